@@ -2,11 +2,17 @@
 """Headline benchmark: images/sec for the whole node (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--model cnn|mlp|resnet50|resnet50_pp]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Default workload = BASELINE.json configs[1] (MNIST CNN DDP bf16, RCCL all-reduce over xGMI); see
 ``pytorch_distributed_examples_amd/bench/harness.py`` for every workload and the timing rules.
+
+A plain run sets up, warms up, times the K steps and prints one JSON result line (``ms_per_step`` = milliseconds per
+timed step).  ``--full`` adds the diagnostics that take runs of their own (per-phase attribution, the timed region's
+fixed cost, the ResNet-50 pipeline at N >= 2); ``--dump-outputs DIR`` writes what the last timed step left (loss,
+parameters, gradients) as ``DIR/<name>.npy``.
 
 ``--gpus N`` with N > 1 and no torchrun environment: this process launches the N ranks itself (torchrun on
 127.0.0.1, one rank per GPU) WITHOUT touching the GPU first, passes its own arguments through and exits with

@@ -34,6 +34,12 @@ Every timed step is a complete training step (forward, backward, gradient all-re
 steps are recorded into hipGraphs (several steps per replay for the launch-bound MNIST nets).  W warmup steps
 run untimed; then K steps are timed between barrier + synchronize pairs and the MAX over ranks is taken.
 
+A plain run stops there: set up, warm up, time the K steps, print the result line.  ``--full`` adds the diagnostics
+that take runs of their own after the timed region: the per-phase attribution (``config.phases``), the timed
+region's fixed cost (``config.region_overheads``) and, at N >= 2, BASELINE configs 3/4 in child processes
+(``config.secondary``).  ``--dump-outputs DIR`` writes what the last timed step left -- its loss, the parameters and
+the gradients -- as ``DIR/<name>.npy``; seeds are fixed, so equal arguments give equal inputs from run to run.
+
 Multi-GPU runs verify themselves: the world size must equal ``--gpus``, and every rank all-reduces a
 checksum over the GPU data-plane communicator and reads back RCCL's own rank count (``rccl_nranks``).
 """
@@ -101,6 +107,13 @@ def parse_args(argv=None):
                          "already replayed")
     ap.add_argument("--generic", action="store_true", help="CNN / MLP: layer-by-layer autograd kernels instead of the fused step")
     ap.add_argument("--device", default="auto", choices=["auto", "cpu"], help="cpu: contract/plumbing check only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also take the diagnostics that need runs of their own: the per-phase "
+                         "attribution (config.phases), the timed region's fixed cost (config.region_overheads) and, at "
+                         "N >= 2, the ResNet-50 pipeline in child processes (config.secondary)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step left (loss, parameters, gradients) "
+                         "as DIR/<name>.npy (float32; rank 0)")
     args = ap.parse_args(argv)
     if args.graph_steps <= 0:
         def divisor_upto(cap):
@@ -146,6 +159,30 @@ def _data_plane_check(ctx, comm) -> int:
     if nranks != n:
         raise RuntimeError(f"rank {ctx.rank}: communicator reports {nranks} ranks, world is {n}")
     return nranks
+
+
+def _flat(tensors):
+    return torch.cat([t.detach().float().reshape(-1) for t in tensors])
+
+
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MB of float32 (loss + parameters + gradients stay under 64 MB in all)
+
+
+def dump_outputs(path, loss, arrays):
+    """``--dump-outputs``: the last timed step's loss and the state it left, one float32 ``.npy`` per array.  An array
+    of more than DUMP_MAX_ELEMS elements is written as a fixed sample of that many (the same seeded, sorted indices
+    every run), so two builds can be compared output for output."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    if loss is not None:
+        arrays = dict(loss=loss, **arrays)
+    for name, t in arrays.items():
+        t = t.detach().float().reshape(-1).cpu()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(0)
+            t = t[torch.randperm(t.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values]
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
 
 
 _UNIT_GRADS: dict = {}
@@ -398,6 +435,16 @@ def build_data_parallel(args, ctx, batch) -> Workload:
     w.phase_step = phase_step
     w.phase_inputs = lambda: list(batch_fn(0))
     w.phase_call = lambda timer, x, y: train_step(x, y, timer)
+
+    def outputs():
+        # the one-launch MLP step updates each weight tile straight from its gradient accumulators: no gradients
+        # are left in memory
+        out = {"params": _flat(model.parameters())}
+        if mega is None:
+            out["grads"] = _flat(p.grad for p in model.parameters() if p.grad is not None)  # views of the DDP buffer
+        return out
+
+    w.outputs = outputs
     if fused is not None and ctx.world_size == 1:
         w.kernel_stamps = _cnn_kernel_stamps(fused, batch, dev)
     return w
@@ -536,6 +583,8 @@ def build_hvd_cnn(args, ctx, batch) -> Workload:
     w.check = check
     w.mark = mark
     w.close = hvd.shutdown
+    w.outputs = lambda: {"params": _flat(model.parameters()),
+                         "grads": grads if grads is not None else _flat(p.grad for p in model.parameters())}
     return w
 
 
@@ -598,6 +647,7 @@ def build_pipeline(args, ctx, batch) -> Workload:
     w.phase_inputs = lambda: []
     w.phase_call = lambda timer: pipe.step(timer)
     w.per_stage = True
+    w.outputs = lambda: {"params": _flat(pipe.module.parameters())}  # this rank's stage
     return w
 
 
@@ -774,6 +824,8 @@ def main(argv=None):
     if args.model == "elastic_cnn":  # BASELINE config 2 (bench/elastic.py); bench.py runs it without torchrun
         from . import elastic
 
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: not available for --model elastic_cnn (its workers end with the rounds)")
         if args.elastic_worker:
             return elastic.worker(args)
         bench_py = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))),
@@ -814,9 +866,13 @@ def main(argv=None):
         check_device_errors(f"rank {ctx.rank} after the timed region")
     dt = pdist.max_over_ranks(dt, ctx.device)
     final_loss = _report_loss(work, ctx, loss)
-    phases = _measure_phases(work, ctx, args) if os.environ.get("PDE_BENCH_PHASES", "1") != "0" else None
+    if args.dump_outputs and ctx.rank == 0:  # before the --full diagnostics below run further steps
+        dump_outputs(args.dump_outputs, torch.tensor([final_loss], dtype=torch.float32), work.outputs())
+    # everything below the timed region that runs steps of its own is --full only (PDE_BENCH_PHASES / _OVERHEADS /
+    # _SECONDARY = 0 still switch single diagnostics off there)
+    phases = _measure_phases(work, ctx, args) if args.full and os.environ.get("PDE_BENCH_PHASES", "1") != "0" else None
     overheads = None
-    if on_gpu and work.group is not None and os.environ.get("PDE_BENCH_OVERHEADS", "1") != "0":
+    if args.full and on_gpu and work.group is not None and os.environ.get("PDE_BENCH_OVERHEADS", "1") != "0":
         try:
             overheads = _region_overheads(work, ctx)
         except Exception as exc:  # noqa: BLE001 - diagnostics never cost the headline line
@@ -824,7 +880,7 @@ def main(argv=None):
     value = work.images_per_step * args.steps / dt
     secondary = None
     mode = os.environ.get("PDE_BENCH_SECONDARY", "1")  # 0: off; force: also on CPU/gloo (plumbing tests)
-    if (args.model == "cnn" and ctx.world_size >= 2 and ctx.world_size % 2 == 0 and mode != "0" and
+    if (args.full and args.model == "cnn" and ctx.world_size >= 2 and ctx.world_size % 2 == 0 and mode != "0" and
             "PDE_BENCH_CHILD" not in os.environ and (mode == "force" or (on_gpu and ctx.backend == "nccl"))):
         secondary = _secondary_pipeline(ctx)
     same_shape = args.image is None and batch == DEFAULT_BATCH[args.model]

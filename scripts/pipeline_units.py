@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Predicted 2-GPU pipeline step of the ResNet-50 split (BASELINE configs 3/4) per pipeline-unit size, from the
-measured single-stage times (bench.py --model resnet50_stage --stage s --batch 8g --mb-group g) and the measured
+measured single-stage times (bench.py --full --model resnet50_stage --stage s --batch 8g --mb-group g) and the measured
 whole-model 1-GPU step (bench.py --model resnet50), side by side.
 
 A batch of 32 images in micro-batches of m = 8 (the reference's split size) is U = 4 / g units of g micro-batches.

@@ -33,6 +33,33 @@ def test_bench_cpu_single():
     assert rec["config"]["global_batch"] == 32 and rec["config"]["parallelism"] == "dp1"
 
 
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run carries no diagnostics that take steps of their own; ``--full`` adds them after the timed region.
+    ``--dump-outputs`` writes the last timed step's loss, parameters and gradients: same arguments, same arrays (the
+    ``--full`` run's too, since they are written before its extra steps)."""
+    import numpy as np
+
+    recs = []
+    for name, extra in (("plain", []), ("full", ["--full"])):
+        rc, out = run_cmd(["python", os.path.join(REPO, "bench.py"), "--gpus", "1", "--device", "cpu", "--steps", "3",
+                           "--warmup", "1", "--batch", "32", "--dump-outputs", str(tmp_path / name), *extra],
+                          timeout=300)
+        assert rc == 0, out
+        recs.append(_parse(out))
+    plain, full = recs
+    assert not {"phases", "region_overheads", "secondary"} & set(plain["config"]), plain["config"]
+    assert set(full["config"]["phases"]["rank0_ms"]) >= {"fwd", "bwd", "opt"}, full["config"]
+    assert plain["steps"] == full["steps"] == 3 and plain["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path / "plain")) == ["grads.npy", "loss.npy", "params.npy"]
+    for f in ("grads.npy", "loss.npy", "params.npy"):
+        a, b = np.load(tmp_path / "plain" / f), np.load(tmp_path / "full" / f)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), f
+        assert np.array_equal(a, b), f
+    assert np.load(tmp_path / "plain" / "params.npy").size == np.load(tmp_path / "plain" / "grads.npy").size == 21840
+    assert abs(float(np.load(tmp_path / "plain" / "loss.npy")[0]) - plain["config"]["final_loss"]) < 1e-4
+    assert np.abs(np.load(tmp_path / "plain" / "grads.npy")).max() > 0
+
+
 def test_bench_cpu_torchrun_world2():
     rc, out = run_cmd(["python", "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                        "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(REPO, "bench.py"),
@@ -72,12 +99,12 @@ def test_bench_resnet_pipeline_world2():
 
 
 def test_bench_secondary_pipeline_measurement():
-    """At N >= 2 the headline run also measures BASELINE config 3/4 (resnet50_pp) in child processes and
+    """At N >= 2 the ``--full`` headline run also measures BASELINE config 3/4 (resnet50_pp) in child processes and
     reports it under config.secondary (forced on CPU here, tiny images)."""
     env = {"PDE_BENCH_SECONDARY": "force",
            "PDE_BENCH_SECONDARY_ARGS": "--device cpu --batch 4 --split-size 2 --image 32 --steps 1 --warmup 1"}
     rc, out = run_cmd(["python", os.path.join(REPO, "bench.py"), "--gpus", "2", "--device", "cpu", "--steps", "2",
-                       "--warmup", "1", "--batch", "16"], timeout=300, env=env)
+                       "--warmup", "1", "--batch", "16", "--full"], timeout=300, env=env)
     assert rc == 0, out
     rec = _parse(out)
     sec = rec["config"]["secondary"]

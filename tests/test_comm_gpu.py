@@ -222,6 +222,31 @@ def test_hvd_cnn_bench_world1_graph(gpu):
     assert rec["config"]["hipgraph"] and rec["config"]["fused_step"] and rec["value"] > 1e6, rec
 
 
+def test_flagship_bench_plain_run_dumps_outputs(gpu, tmp_path):
+    """The plain flagship run (fused CNN step in hipGraphs) takes no diagnostics of its own and ``--dump-outputs``
+    writes the last timed step's loss, the 21,840 parameters and their gradients as float32 arrays."""
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup",
+                          "5", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300,
+                         env=_clean_env())
+    assert res.returncode == 0, res.stderr[-3000:]
+    rec = _bench_json(res.stdout)
+    assert rec["steps"] == 20 and rec["ms_per_step"] > 0 and rec["config"]["fused_step"] and rec["config"]["hipgraph"]
+    assert not {"phases", "region_overheads", "secondary"} & set(rec["config"]), rec["config"]
+    assert sorted(os.listdir(tmp_path)) == ["grads.npy", "loss.npy", "params.npy"]
+    loss, params, grads = (np.load(tmp_path / f"{n}.npy") for n in ("loss", "params", "grads"))
+    assert loss.dtype == params.dtype == grads.dtype == np.float32
+    assert loss.shape == (1,) and params.shape == grads.shape == (21840,)
+    assert np.isfinite(params).all() and np.isfinite(grads).all() and np.abs(grads).max() > 0
+    # 25 SGD steps from the random init: the loss is still near ln 10 and is the one the record reports
+    assert abs(float(loss[0]) - rec["config"]["final_loss"]) < 1e-4 and 1.5 < float(loss[0]) < 3.0
+
+
 def test_hvd_cnn_world2_one_gpu_rehearsal(gpu):
     """Two Horovod ranks sharing the card (RCCL refuses that; the engine's xGMI one-shot data plane does
     not): the first step negotiates through the fusion engine, then graph mode reduces the flat gradient
