@@ -32,6 +32,9 @@ void check(hipError_t e, const char* what) {
 #define CHECK_CONTIG(x) TORCH_CHECK((x).is_contiguous(), #x " must be contiguous")
 #define CHECK_BF16(x) TORCH_CHECK((x).scalar_type() == at::kBFloat16, #x " must be bf16")
 #define CHECK_F32(x) TORCH_CHECK((x).scalar_type() == at::kFloat, #x " must be fp32")
+// (kernels that read fp32 or bf16 through one `f32` flag: anything else would be read as bf16)
+#define CHECK_F32_OR_BF16(x)                                                                \
+  TORCH_CHECK((x).scalar_type() == at::kFloat || (x).scalar_type() == at::kBFloat16, #x " must be fp32 or bf16")
 #define CHECK_IN(x) \
   CHECK_DEV(x);     \
   CHECK_CONTIG(x)
@@ -387,7 +390,7 @@ void gather_rows_counter(const Tensor& src, const Tensor& labels, const Tensor& 
 // (mean cross-entropy loss, d loss / d logits as bf16) in one launch.  dx_out: a [B, >= V] bf16 row view to
 // write d logits into (its columns past V are left as they are, e.g. the zero padding of a K = 16 operand).
 std::vector<Tensor> ce_fused(const Tensor& x, const Tensor& tgt, const optional<Tensor>& dx_out) {
-  CHECK_IN(x); CHECK_IN(tgt);
+  CHECK_IN(x); CHECK_IN(tgt); CHECK_F32_OR_BF16(x);
   TORCH_CHECK(tgt.scalar_type() == at::kLong, "targets must be int64");
   const int B = x.size(0), V = x.size(1);
   Tensor loss = at::empty({}, x.options().dtype(at::kFloat));
@@ -750,7 +753,7 @@ Tensor relu_bwd(const Tensor& dy, const Tensor& y) {
 // Losses
 // ------------------------------------------------------------------------------------------------
 std::vector<Tensor> ce_fwd(const Tensor& x, const Tensor& tgt, int mode) {
-  CHECK_IN(x); CHECK_IN(tgt);
+  CHECK_IN(x); CHECK_IN(tgt); CHECK_F32_OR_BF16(x);
   TORCH_CHECK(tgt.scalar_type() == at::kLong, "targets must be int64");
   const int B = x.size(0), V = x.size(1);
   TORCH_CHECK(B <= 1 << 20, "batch too large for the single-block reduction");
@@ -763,7 +766,7 @@ std::vector<Tensor> ce_fwd(const Tensor& x, const Tensor& tgt, int mode) {
   return {loss, lse};
 }
 Tensor ce_bwd(const Tensor& x, const Tensor& tgt, const Tensor& lse, const Tensor& gout, int mode, bool dx_f32) {
-  CHECK_IN(x); CHECK_IN(tgt); CHECK_IN(gout);
+  CHECK_IN(x); CHECK_IN(tgt); CHECK_IN(gout); CHECK_F32_OR_BF16(x);
   const int B = x.size(0), V = x.size(1);
   const bool f = x.scalar_type() == at::kFloat;
   Tensor dx = at::empty({B, V}, x.options().dtype(dx_f32 ? at::kFloat : at::kBFloat16));
@@ -773,7 +776,7 @@ Tensor ce_bwd(const Tensor& x, const Tensor& tgt, const Tensor& lse, const Tenso
   return dx;
 }
 Tensor log_softmax_fwd(const Tensor& x) {
-  CHECK_IN(x);
+  CHECK_IN(x); CHECK_F32_OR_BF16(x);
   const int B = x.size(0), V = x.size(1);
   Tensor y = at::empty({B, V}, x.options().dtype(at::kFloat));
   check(pde::log_softmax_fwd(x.data_ptr(), x.scalar_type() == at::kFloat, B, V, y.data_ptr<float>(), cur_stream()),
@@ -789,7 +792,7 @@ Tensor log_softmax_bwd(const Tensor& dy, const Tensor& y, bool dx_f32) {
   return dx;
 }
 Tensor mse_fwd(const Tensor& p, const Tensor& t) {
-  CHECK_IN(p); CHECK_IN(t); CHECK_F32(t);
+  CHECK_IN(p); CHECK_IN(t); CHECK_F32(t); CHECK_F32_OR_BF16(p);
   Tensor loss = at::empty({}, p.options().dtype(at::kFloat));
   check(pde::mse_fwd(p.data_ptr(), p.scalar_type() == at::kFloat, t.data_ptr<float>(), p.numel(),
                      loss.data_ptr<float>(), cur_stream()),
@@ -797,7 +800,7 @@ Tensor mse_fwd(const Tensor& p, const Tensor& t) {
   return loss;
 }
 Tensor mse_bwd(const Tensor& p, const Tensor& t, const Tensor& gout, bool dx_f32) {
-  CHECK_IN(p); CHECK_IN(t); CHECK_IN(gout);
+  CHECK_IN(p); CHECK_IN(t); CHECK_IN(gout); CHECK_F32_OR_BF16(p);
   Tensor dx = at::empty(p.sizes(), p.options().dtype(dx_f32 ? at::kFloat : at::kBFloat16));
   check(pde::mse_bwd(p.data_ptr(), p.scalar_type() == at::kFloat, t.data_ptr<float>(), gout.data_ptr<float>(),
                      p.numel(), dx.data_ptr(), dx_f32, cur_stream()),

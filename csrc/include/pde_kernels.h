@@ -217,7 +217,10 @@ struct OptimEntry {
 struct OptimChunk {      // elements [start, start + count) of tensor `tensor`
   int tensor, start, count, pad;
 };
-enum HParam { HP_LR = 0, HP_BETA1, HP_BETA2, HP_EPS, HP_WD, HP_MOMENTUM, HP_GRAD_SCALE, HP_COUNT };
+// HP_OMB1 / HP_OMB2: 1 - beta1 / 1 - beta2, taken in double on the host and then rounded.  fp32 (1 - 0.999f) is
+// off by 1.3e-5 relative (the rounding of 0.999 seen from the 0.001 end), and so were exp_avg_sq and the step-1
+// bias correction computed from it.
+enum HParam { HP_LR = 0, HP_BETA1, HP_BETA2, HP_EPS, HP_WD, HP_MOMENTUM, HP_GRAD_SCALE, HP_OMB1, HP_OMB2, HP_COUNT };
 int optim_chunk_elems();  // chunk size the host must cut tensors into
 // A range of optimiser chunks [c0, c1) run by `blocks` extra blocks appended to a GEMM pair launch
 // (gemm_bf16_pair) -- or by its own launch (multi_tensor_optim_range).  publish: this segment is the step's

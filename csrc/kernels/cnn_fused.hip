@@ -1479,14 +1479,7 @@ __global__ __launch_bounds__(256) void k_cnn_adamw(float* __restrict__ params, c
   __shared__ int s_step;
   if (threadIdx.x == 0) s_step = step[0] + 1;
   __syncthreads();
-  optdev::Hyper h;
-  h.lr = hp[HP_LR]; h.b1 = hp[HP_BETA1]; h.b2 = hp[HP_BETA2]; h.eps = hp[HP_EPS];
-  h.wd = hp[HP_WD]; h.mom = hp[HP_MOMENTUM]; h.gscale = hp[HP_GRAD_SCALE];
-  h.step = s_step;
-  const float bc1 = 1.f - __powf(h.b1, static_cast<float>(h.step));
-  const float bc2 = 1.f - __powf(h.b2, static_cast<float>(h.step));
-  h.step_size = h.lr / bc1;
-  h.inv_sqrt_bc2 = rsqrtf(bc2);
+  const optdev::Hyper h = optdev::load_hyper<2>(hp, s_step);
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p < NPARAM) {
     float w = params[p], mm = m[p], vv = v[p];

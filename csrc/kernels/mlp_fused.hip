@@ -794,18 +794,7 @@ __global__ __launch_bounds__(MT) void k_mlp_train(MlpTrainArgs a) {
   __syncthreads();
   const int nbar = 2 * a.nl - 1;  // F0..F(L-2), CE, B(L-1)..B1
   const Bar bar{a.bar, s_launch * static_cast<unsigned>(nbar)};
-  optdev::Hyper h;
-  h.lr = a.hp[HP_LR]; h.b1 = a.hp[HP_BETA1]; h.b2 = a.hp[HP_BETA2]; h.eps = a.hp[HP_EPS];
-  h.wd = a.hp[HP_WD]; h.mom = a.hp[HP_MOMENTUM]; h.gscale = a.hp[HP_GRAD_SCALE];
-  h.step = s_step;
-  h.step_size = 0.f;
-  h.inv_sqrt_bc2 = 1.f;
-  if (MODE != 0) {
-    const float bc1 = 1.f - __powf(h.b1, static_cast<float>(h.step));
-    const float bc2 = 1.f - __powf(h.b2, static_cast<float>(h.step));
-    h.step_size = h.lr / bc1;
-    h.inv_sqrt_bc2 = rsqrtf(bc2);
-  }
+  const optdev::Hyper h = optdev::load_hyper<MODE>(a.hp, s_step);
   const bool use_m = MODE != 0 || h.mom != 0.f;
   const int nl = a.nl, B = a.B;
   RowLoads R;

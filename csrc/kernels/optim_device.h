@@ -15,29 +15,54 @@ constexpr int kOptGroups = 4;                       // 16-byte groups per thread
 constexpr int kOptChunk = kOptThreads * 4 * kOptGroups;   // elements per chunk (4096)
 
 struct Hyper {
-  float lr, b1, b2, eps, wd, mom, gscale, step_size, inv_sqrt_bc2;
+  float lr, b1, b2, omb1, omb2, eps, wd, mom, gscale, step_size, inv_sqrt_bc2;
   int step;
 };
 
+// 1 - beta^step from omb = 1 - beta, without cancellation: beta2^step is within 1e-3 of 1 at step 1
+// (beta2 = 0.999), where 1.f - powf(beta, step) keeps 6e-5 relative at best.  Once per block.
+__device__ __forceinline__ float bias_correction(float omb, int step) {
+  return -expm1f(static_cast<float>(step) * log1pf(-omb));
+}
+
+// The hyper-parameters of step `step` (1-based) from the device table (float[HP_COUNT]).
+template <int MODE>
+__device__ __forceinline__ Hyper load_hyper(const float* __restrict__ hp, int step) {
+  Hyper h;
+  h.lr = hp[HP_LR]; h.b1 = hp[HP_BETA1]; h.b2 = hp[HP_BETA2]; h.eps = hp[HP_EPS];
+  h.wd = hp[HP_WD]; h.mom = hp[HP_MOMENTUM]; h.gscale = hp[HP_GRAD_SCALE];
+  h.omb1 = hp[HP_OMB1]; h.omb2 = hp[HP_OMB2];
+  h.step = step;
+  h.step_size = 0.f;
+  h.inv_sqrt_bc2 = 1.f;
+  if (MODE != 0) {
+    h.step_size = h.lr / bias_correction(h.omb1, step);
+    h.inv_sqrt_bc2 = rsqrtf(bias_correction(h.omb2, step));
+  }
+  return h;
+}
+
+// Every operation is spelled out (fmaf / __fmul_rn), so the compiler's FMA contraction cannot differ between the
+// kernels this is inlined into (k_optim, the GEMM pair kernels, the fused MLP / CNN steps): bit-identical updates.
 template <int MODE>
 __device__ __forceinline__ void update(const Hyper& h, float& p, float g, float& m, float& v) {
-  g *= h.gscale;
+  g = __fmul_rn(g, h.gscale);
   if (MODE == 0) {  // SGD (+momentum, +L2)
-    if (h.wd != 0.f) g += h.wd * p;
+    if (h.wd != 0.f) g = fmaf(h.wd, p, g);
     if (h.mom != 0.f) {
-      m = (h.step == 1) ? g : h.mom * m + g;
+      m = (h.step == 1) ? g : fmaf(h.mom, m, g);
       g = m;
     }
-    p -= h.lr * g;
+    p = fmaf(-h.lr, g, p);
   } else {
     if (MODE == 1) {
-      if (h.wd != 0.f) g += h.wd * p;
+      if (h.wd != 0.f) g = fmaf(h.wd, p, g);
     } else {
-      p *= 1.f - h.lr * h.wd;
+      p = __fmul_rn(p, fmaf(-h.lr, h.wd, 1.f));
     }
-    m = h.b1 * m + (1.f - h.b1) * g;
-    v = h.b2 * v + (1.f - h.b2) * g * g;
-    p -= h.step_size * m / (sqrtf(v) * h.inv_sqrt_bc2 + h.eps);
+    m = fmaf(h.b1, m, __fmul_rn(h.omb1, g));
+    v = fmaf(h.b2, v, __fmul_rn(__fmul_rn(h.omb2, g), g));
+    p = fmaf(-h.step_size, __fdiv_rn(m, fmaf(sqrtf(v), h.inv_sqrt_bc2, h.eps)), p);
   }
 }
 
@@ -146,16 +171,7 @@ __device__ __forceinline__ void run_chunks(const OptimEntry* __restrict__ tab, c
   __shared__ int s_step;
   if (threadIdx.x == 0) s_step = step_ptr[0] + 1;  // step being taken (1-based)
   __syncthreads();
-  Hyper h;
-  h.lr = hp[HP_LR]; h.b1 = hp[HP_BETA1]; h.b2 = hp[HP_BETA2]; h.eps = hp[HP_EPS];
-  h.wd = hp[HP_WD]; h.mom = hp[HP_MOMENTUM]; h.gscale = hp[HP_GRAD_SCALE];
-  h.step = s_step;
-  if (MODE != 0) {
-    const float bc1 = 1.f - __powf(h.b1, static_cast<float>(h.step));
-    const float bc2 = 1.f - __powf(h.b2, static_cast<float>(h.step));
-    h.step_size = h.lr / bc1;
-    h.inv_sqrt_bc2 = rsqrtf(bc2);
-  }
+  const Hyper h = load_hyper<MODE>(hp, s_step);
   const bool use_m = MODE != 0 || h.mom != 0.f;
   if constexpr (PIPE) {
     ChunkRegs<MODE, NT> cur, nxt;

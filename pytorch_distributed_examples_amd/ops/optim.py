@@ -40,7 +40,7 @@ class _FusedBase(torch.optim.Optimizer):
         dev = params[0].device
         if st is None:
             st = {"sig": None, "hp_key": None,
-                  "hp": torch.zeros(8, dtype=torch.float32, device=dev),
+                  "hp": torch.zeros(9, dtype=torch.float32, device=dev),  # float[HP_COUNT], pde_kernels.h
                   # {steps taken, arrival counter of the update kernel}
                   "step": torch.zeros(2, dtype=torch.int32, device=dev)}
             # a new group state (new optimizer, or after load_state_dict): the host step is authoritative once
@@ -87,7 +87,8 @@ class _FusedBase(torch.optim.Optimizer):
         b1, b2 = group["betas"]
         hp_key = (group["lr"], b1, b2, group["eps"], group["weight_decay"], group["momentum"], group["grad_scale"])
         if st["hp_key"] != hp_key:
-            st["hp"].copy_(torch.tensor(list(hp_key) + [0.0], dtype=torch.float32), non_blocking=False)
+            # + HP_OMB1 / HP_OMB2: 1 - beta in double, then rounded (the kernel's 1.f - 0.999f is 1.3e-5 off)
+            st["hp"].copy_(torch.tensor(list(hp_key) + [1.0 - b1, 1.0 - b2], dtype=torch.float32), non_blocking=False)
             st["hp_key"] = hp_key
         return st
 
