@@ -86,6 +86,99 @@ constexpr int D2R = O2 * O2 + 8;       // d2 plane row stride (u16): 144 B
 constexpr int MT1 = O1 * O1 / 16;      // 36 conv1 M-tiles per image (4 cells x 4 taps each)
 constexpr int MTD = NC1 * 1 / 16;      // 9 conv2-dgrad M-tiles per image (144 r1 positions)
 constexpr int KSW1 = O1 * O1 / 32;     // 18 conv1-wgrad k-steps per image
+// conv2 dgrad k-step ranges.  A dgrad tile is 16 consecutive row-major positions of the 12x12 plane, so its class
+// c = tile % MTD fixes the two rows Y it covers, and a source row Y - ky exists only for max(0, Y - 7) <= ky <=
+// min(4, Y): with K ordered (ky, kx, co group) the k-steps in which ANY lane of the class reads a real source
+// position are one contiguous run [lo, hi) of the KSD -- outside it every A fragment is the zero block and the
+// MFMA adds exact zeros.  Derived from the geometry, per class; 126 of the 9 x 19 = 171 k-steps remain.
+struct KsRange {
+  int lo, hi;
+};
+__host__ __device__ constexpr bool p7b_tap_live(int cls, int r, int ky, int kx) {  // position r of the class, tap
+  const int pos = cls * 16 + r, y = pos / P1 - ky, x = pos % P1 - kx;
+  return y >= 0 && y < O2 && x >= 0 && x < O2;
+}
+__host__ __device__ constexpr KsRange p7b_ks_range(int cls) {
+  int lo = KSD, hi = 0;
+  for (int r = 0; r < 16; ++r)
+    for (int ky = 0; ky < KS; ++ky)
+      for (int kx = 0; kx < KS; ++kx) {
+        if (!p7b_tap_live(cls, r, ky, kx)) continue;
+        const int g0 = (ky * KS + kx) * CG, k0 = g0 / 4, k1 = (g0 + CG - 1) / 4;  // the tap's co groups' k-steps
+        lo = k0 < lo ? k0 : lo;
+        hi = k1 + 1 > hi ? k1 + 1 : hi;
+      }
+  return {lo, hi};
+}
+// every live (position, tap, co group) of the class lies inside [lo, hi) (checked group by group, not through
+// the derivation's k0 / k1)
+__host__ __device__ constexpr bool p7b_range_covers(int cls, KsRange q) {
+  for (int g = 0; g < NGD; ++g)
+    for (int r = 0; r < 16; ++r)
+      if (p7b_tap_live(cls, r, g / CG / KS, g / CG % KS) && (g / 4 < q.lo || g / 4 >= q.hi)) return false;
+  return q.lo >= 0 && q.hi <= KSD;
+}
+__host__ __device__ constexpr bool p7b_ranges_ok() {
+  int sum = 0;
+  for (int c = 0; c < MTD; ++c) {
+    if (!p7b_range_covers(c, p7b_ks_range(c))) return false;
+    sum += p7b_ks_range(c).hi - p7b_ks_range(c).lo;
+  }
+  return sum == 126;
+}
+constexpr bool ks_is(KsRange q, int lo, int hi) { return q.lo == lo && q.hi == hi; }
+static_assert(MTD == 9 && NC1 % 16 == 0 && p7b_ranges_ok(), "conv2 dgrad: every live tap inside its class's range");
+static_assert(ks_is(p7b_ks_range(0), 0, 7) && ks_is(p7b_ks_range(1), 0, 12) && ks_is(p7b_ks_range(2), 0, 15) &&
+                  ks_is(p7b_ks_range(3), 0, KSD) && ks_is(p7b_ks_range(4), 0, KSD) &&
+                  ks_is(p7b_ks_range(5), 0, KSD) && ks_is(p7b_ks_range(6), 3, KSD) &&
+                  ks_is(p7b_ks_range(7), 7, KSD) && ks_is(p7b_ks_range(8), 12, KSD),
+              "conv2 dgrad k-step ranges (rows 0-1, 1-2, 2-3, 4..7, 8-9, 9-10, 10-11)");
+// the ranges packed 5 bits per class: a wave picks its own with scalar shifts
+__host__ __device__ constexpr uint64_t p7b_pack(bool hi) {
+  uint64_t v = 0;
+  for (int c = 0; c < MTD; ++c)
+    v |= static_cast<uint64_t>(hi ? p7b_ks_range(c).hi : p7b_ks_range(c).lo) << (5 * c);
+  return v;
+}
+constexpr uint64_t P7B_LO = p7b_pack(false), P7B_HI = p7b_pack(true);
+static_assert(KSD < 32 && MTD * 5 <= 64, "5-bit fields");
+// conv2 dgrad wave map: a wave runs the SAME class for two images (0, 1 or 2, 3), so both tiles share one B
+// fragment, one tap table entry and one bound check per k-step.  Classes 1..7 take two waves each; classes 0
+// and MTD - 1 (disjoint 7-step ranges) share the last two waves, which run class 0 and then class MTD - 1 for
+// their image pair.  Four waves share a SIMD's MFMA pipe (wave w on SIMD w % 4): the six 19-step waves and the
+// rest are dealt so that every SIMD carries 124-128 of the 504 tile-k-steps.
+constexpr int P7B_WCLS[NW] = {3, 4, 5, 5, 3, 4, 6, 6, 1, 7, 2, 2, 1, 7, 0, 0};
+constexpr int P7B_WPAIR[NW] = {0, 0, 0, 1, 1, 1, 0, 1, 0, 0, 0, 1, 1, 1, 0, 1};
+__host__ __device__ constexpr int p7b_wave_steps(int w) {  // tile-k-steps of wave w (two tiles per k-step)
+  const int c = P7B_WCLS[w];
+  int n = p7b_ks_range(c).hi - p7b_ks_range(c).lo;
+  if (c == 0) n += p7b_ks_range(MTD - 1).hi - p7b_ks_range(MTD - 1).lo;
+  return 2 * n;
+}
+__host__ __device__ constexpr bool p7b_map_ok() {
+  for (int c = 0; c < MTD - 1; ++c) {  // every (class, pair) on exactly one wave (class MTD - 1 rides with 0)
+    int n[2] = {0, 0};
+    for (int w = 0; w < NW; ++w)
+      if (P7B_WCLS[w] == c) ++n[P7B_WPAIR[w]];
+    if (n[0] != 1 || n[1] != 1) return false;
+  }
+  int tot = 0;
+  for (int s = 0; s < 4; ++s) {
+    int n = 0;
+    for (int w = s; w < NW; w += 4) n += p7b_wave_steps(w);
+    if (n < 120 || n > 132) return false;
+    tot += n;
+  }
+  return tot == NI * 126;
+}
+static_assert(NW == 16 && NI == 4 && p7b_map_ok(), "conv2 dgrad wave map: complete, balanced over the SIMDs");
+__host__ __device__ constexpr uint64_t p7b_pack_map(bool pair) {
+  uint64_t v = 0;
+  for (int w = 0; w < NW; ++w) v |= static_cast<uint64_t>(pair ? P7B_WPAIR[w] : P7B_WCLS[w]) << (4 * w);
+  return v;
+}
+constexpr uint64_t P7B_MCLS = p7b_pack_map(false), P7B_MPAIR = p7b_pack_map(true);
+constexpr int XMAP_P7B_FULLK = 8;  // xmap bit: every class runs all KSD k-steps (PDE_CNN_P7B_FULLK, diagnostic)
 // parameter offsets in the flat gradient (torch parameter order of Net)
 constexpr int O_W1 = 0, O_B1 = O_W1 + W1N, O_W2 = O_B1 + C1, O_B2 = O_W2 + W2N, O_FC1W = O_B2 + C2,
               O_FC1B = O_FC1W + FC1N, O_FC2W = O_FC1B + F1, O_FC2B = O_FC2W + FC2N, NPARAM = O_FC2B + F2;
@@ -216,6 +309,23 @@ __device__ __forceinline__ void lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+// An LDS address as the 32-bit offset a ds_read takes, and a 16-byte read at one: P7b selects between two
+// addresses per read, which has to stay a select of integers (k_cnn_train)
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)(const __attribute__((address_space(3))) unsigned char*)(p);
+#else
+  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>(p));
+#endif
+}
+__device__ __forceinline__ u16x8 lds_read16(uint32_t o) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return *(const __attribute__((address_space(3))) u16x8*)(o);
+#else
+  return u16x8{static_cast<uint16_t>(o), 0, 0, 0, 0, 0, 0, 0};
+#endif
 }
 
 // Single-process fused tail (cnn_train_fused with PDE_CNN_FUSED_TAIL): after P9 every workgroup of k_cnn_train
@@ -783,95 +893,146 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
   PDE_STAMP(9);
 
   // ---- P7b: conv2 dgrad (MFMA): dr1[ci][Y][X] = sum_(ky,kx) sum_co d2[Y-ky][X-kx][co] * w2[co][ci][ky][kx],
-  // then relu'(r1).  M = r1 positions (9 tiles per image, 36 total, round-robin over waves), N = ci,
-  // K = (tap, co24) packed into 19 k-steps: a lane's A fragment is the 16-byte co-group of ITS tap's source
-  // position (Y-ky, X-kx), or the zero block when that position lies outside the 8x8 conv2 output -- every
-  // read is unconditional, so the k-loop pipelines its LDS reads ahead of the MFMAs.
+  // then relu'(r1).  M = r1 positions (9 tiles per image, 36 total), N = ci, K = (tap, co24) packed into 19
+  // k-steps: a lane's A fragment is the 16-byte co-group of ITS tap's source position (Y-ky, X-kx), or the zero
+  // block when that position lies outside the 8x8 conv2 output -- every read is unconditional, so the k-loop
+  // pipelines its LDS reads ahead of the MFMAs.  A wave owns one tile class for two images (P7B_WCLS): its two
+  // tiles cover the same positions, so they share the B fragment, the tap entry and the bound check of a k-step,
+  // and the k-loop runs only the class's k-steps (p7b_ks_range: the others add exact zeros, so the sums keep
+  // their bits).  The phase is bound by LDS fragment reads and VALU issue, both per (tile, k-step).
   {
-    constexpr int MAXT = (NI * MTD + NW - 1) / NW;  // 3
-    f32x4 acc[MAXT];
-    int ty[MAXT], tx[MAXT], tb[MAXT];
-    u16x2 tyx[MAXT];  // (ty, tx) packed: one packed subtract checks both tap offsets
-#pragma unroll
-    for (int u = 0; u < MAXT; ++u) {
-      acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const int tile = min(wid + u * NW, NI * MTD - 1);  // a 2-tile wave's third slot mirrors a real tile
-      // (4x4-block tiles model fewer bank conflicts, 6.8 -> 6.0 LDS cycles per A read, but measured slower:
-      // P7b 5.76 -> 5.96 us, r4t)
-      const int im = tile / MTD, pos = (tile % MTD) * 16 + lr;
-      ty[u] = pos / P1;
-      tx[u] = pos - ty[u] * P1;
-      tb[u] = d2n_ofs(im, ty[u], tx[u], 0) * 2;  // byte offset at tap (0,0), channel 0
-      tyx[u] = u16x2{static_cast<uint16_t>(tx[u]), static_cast<uint16_t>(ty[u])};
-    }
-    const char* base = reinterpret_cast<const char*>(&S.d2n[0]);
-    const char* zp = reinterpret_cast<const char*>(&S.zero16[0]);
-    const char* tp[MAXT];  // each tile's tap-(0,0) address: a k-step adds the tap offset and selects
-#pragma unroll
-    for (int u = 0; u < MAXT; ++u) tp[u] = base + tb[u];
-    const int ntile = wid < NI * MTD - 2 * NW ? 3 : 2;  // wave-uniform (36 tiles over 16 waves)
-
-    // k-step ks, lane group lg: tap / co group of k-group g = 4 ks + lg from the LDS table (one 8-byte read
-    // instead of the divisions), validity of (Y - ky, X - kx) for all tiles by one packed 16-bit subtract each
-    // (r4af: P7b was the phase with the most VALU instructions)
-    // (table entries are read one k-step before the loads that use them: the read's latency hides under the
-    // previous k-step's MFMAs)
-    auto tab = [&](int ks) { return *reinterpret_cast<const u32x2*>(&S.p7tab[min(ks, KSD - 1) * 4 + lg][0]); };
-    auto load = [&](auto ntc, int ks, const u32x2& e, u16x8 (&a)[MAXT], u16x8& b) {
-      const u16x2 kyx = __builtin_bit_cast(u16x2, e[0]);
-      const int tofs = static_cast<int>(e[1]);
-      if constexpr (BREG) b = bd[ks];
-      else b = S.w2d[ks][lane];
-#pragma unroll
-      for (int u = 0; u < decltype(ntc)::value; ++u) {
-        const bool ok = (__builtin_bit_cast(uint32_t, static_cast<u16x2>(tyx[u] - kyx)) & 0xFFF8FFF8u) == 0u;
-        a[u] = *reinterpret_cast<const u16x8*>(ok ? tp[u] + tofs : zp);
-      }
-    };
-    // the k-loop per tile count: a 2-tile wave neither reads nor multiplies a third tile (the phase is bound by
-    // LDS bandwidth, and the mirrored third tile's A reads were ~20% of its bytes)
-    auto kloop = [&](auto ntc) {
-      constexpr int NT = decltype(ntc)::value;
-      u16x8 an[MAXT], bn;
-      load(ntc, 0, tab(0), an, bn);
-      u32x2 en = tab(1);
-#pragma unroll
-      for (int ks = 0; ks < KSD; ++ks) {  // reads of k-step ks+1 are issued before the MFMAs of ks
-        u16x8 ac[MAXT], bc = bn;
-#pragma unroll
-        for (int u = 0; u < NT; ++u) ac[u] = an[u];
-        if constexpr (BREG) {
-          if (ks + KSB < KSD) bd[ks + KSB] = frag[NF2F + (ks + KSB) * 64 + lane];
-        }
-        if (ks + 1 < KSD) {
-          const u32x2 e = en;
-          en = tab(ks + 2);
-          load(ntc, ks + 1, e, an, bn);
-        }
-#pragma unroll
-        for (int u = 0; u < NT; ++u) acc[u] = mfma(ac[u], bc, acc[u]);
-      }
-    };
-    if (ntile == 3) kloop(std::integral_constant<int, 3>{});
-    else kloop(std::integral_constant<int, 2>{});
-    // epilogue: the lane's 4 consecutive cells as e1 words (relu'(r1) from a1's dead mark), one 16-byte store.
+    constexpr int MAXT = 2;
+    const int cls0 = static_cast<int>(P7B_MCLS >> (4 * wid)) & 15;            // wave-uniform, scalar
+    const int im0 = (static_cast<int>(P7B_MPAIR >> (4 * wid)) & 1) * MAXT;    // images im0, im0 + 1
+    const int npass = cls0 == 0 ? 2 : 1;  // the class-0 waves go on with class MTD - 1
+    // (BREG keeps every k-step: a run-time index into its register-held fragments would go to scratch)
+    const bool fullk = BREG || (xmap & XMAP_P7B_FULLK) != 0;
+    // LDS addresses as 32-bit offsets (the A reads select between two of them)
+    const uint32_t sbase = lds_addr(smem_raw);
+    const uint32_t zpo = sbase + static_cast<uint32_t>(offsetof(CnnSmem, zero16));  // the zero block
+    constexpr uint32_t IMB = D2N_IM * 2;  // bytes between the two images' slots
     // e1 aliases r1n / w2f, which no P7a / P7b wave reads (r1 itself is still P7a's B operand: no barrier here)
     uint32_t* e1 = reinterpret_cast<uint32_t*>(&S.r1n[0][0][0]);
+    auto run_pass = [&](int pass) {
+      const int cls = pass == 0 ? cls0 : MTD - 1;
+      const int lo = fullk ? 0 : static_cast<int>(P7B_LO >> (5 * cls)) & 31;
+      const int hi = fullk ? KSD : static_cast<int>(P7B_HI >> (5 * cls)) & 31;
+      // (4x4-block tiles model fewer bank conflicts, 6.8 -> 6.0 LDS cycles per A read, but measured slower:
+      // P7b 5.76 -> 5.96 us, r4t)
+      const int pos = cls * 16 + lr, ty = pos / P1, tx = pos - ty * P1;
+      // (ty, tx) packed: one packed subtract checks both tap offsets
+      const u16x2 tyx{static_cast<uint16_t>(tx), static_cast<uint16_t>(ty)};
+      // LDS byte offset of tap (0,0), channel 0 of the first image: a k-step adds the tap offset and selects
+      const uint32_t tpo = sbase + static_cast<uint32_t>(offsetof(CnnSmem, d2n)) + d2n_ofs(im0, ty, tx, 0) * 2;
+      f32x4 acc[MAXT];
 #pragma unroll
-    for (int u = 0; u < MAXT; ++u) {
-      const int tile = wid + u * NW;
-      const int ci = lr;
-      if (tile < NI * MTD && ci < C1) {
-        const int im = tile / MTD, cell = (tile % MTD) * 16 + lg * 4;
-        const uint32_t am4 = *reinterpret_cast<const uint32_t*>(&S.a1[im][ci * RP8 + cell]);
-        u32x4 e;
+      for (int u = 0; u < MAXT; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+      // the epilogue's argmax / dead marks of the lane's 4 cells, read ahead of the k-loop (rows ci >= C1 are
+      // discarded: they read channel C1 - 1)
+      const int ci = lr, cell = cls * 16 + lg * 4;
+      uint32_t am4[MAXT];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const uint32_t am = (am4 >> (8 * r)) & 0xFFu;
-          e[r] = am == AM_DEAD ? 0u : static_cast<uint32_t>(f2bf(acc[u][r])) << (16 * (am & 1u));
+      for (int u = 0; u < MAXT; ++u)
+        am4[u] = *reinterpret_cast<const uint32_t*>(&S.a1[im0 + u][min(ci, C1 - 1) * RP8 + cell]);
+
+      // k-step ks, lane group lg: tap / co group of k-group g = 4 ks + lg from the LDS table (one 8-byte read
+      // instead of the divisions), validity of (Y - ky, X - kx) by one packed 16-bit subtract
+      // (r4af: P7b was the phase with the most VALU instructions)
+      // (table entries are read one k-step before the loads that use them: the read's latency hides under the
+      // previous k-step's MFMAs)
+      auto tab = [&](int ks) { return *reinterpret_cast<const u32x2*>(&S.p7tab[min(ks, KSD - 1) * 4 + lg][0]); };
+      auto load = [&](const u32x2& e, u16x8 (&a)[MAXT]) {
+        const u16x2 kyx = __builtin_bit_cast(u16x2, e[0]);
+        const bool ok = (__builtin_bit_cast(uint32_t, static_cast<u16x2>(tyx - kyx)) & 0xFFF8FFF8u) == 0u;
+        const uint32_t src = tpo + e[1];
+#pragma unroll
+        for (int u = 0; u < MAXT; ++u) {
+          // the address is selected, never the loaded value (the empty asm keeps it a v_cndmask: with one
+          // condition for both tiles the compiler otherwise branches around the reads and waits inside)
+          uint32_t o = ok ? src + u * IMB : zpo;
+          asm("" : "+v"(o));
+          a[u] = lds_read16(o);
         }
-        *reinterpret_cast<u32x4*>(&e1[(im * C1 + ci) * EP + cell]) = e;
+      };
+      if constexpr (BREG) {
+        u16x8 an[MAXT];
+        load(tab(0), an);
+        u32x2 en = tab(1);
+#pragma unroll
+        for (int ks = 0; ks < KSD; ++ks) {  // reads of k-step ks+1 are issued before the MFMAs of ks
+          u16x8 ac[MAXT];
+#pragma unroll
+          for (int u = 0; u < MAXT; ++u) ac[u] = an[u];
+          if (ks + KSB < KSD) bd[ks + KSB] = frag[NF2F + (ks + KSB) * 64 + lane];
+          if (ks + 1 < KSD) {
+            const u32x2 e = en;
+            en = tab(ks + 2);
+            load(e, an);
+          }
+#pragma unroll
+          for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ac[u], bd[ks], acc[u]);
+        }
+        if (pass + 1 < npass) {  // the second class starts over from k-step 0
+#pragma unroll
+          for (int ks = 0; ks < KSB; ++ks) bd[ks] = frag[NF2F + ks * 64 + lane];
+        }
+      } else {
+        // a scalar-counted loop over [lo, hi), two k-steps per trip on alternating operand registers (ae / be,
+        // ao / bo): reads of k-step ks+1 are issued before the MFMAs of ks, one accumulator per tile in ascending
+        // ks.  (The 19 steps unrolled, each under a wave-uniform lo <= ks < hi guard, index w2d / p7tab by
+        // constants but measured no faster than without ranges: P7b 4.44 against 3.88 us, 34.5 against 28.1 KB
+        // of code, profiles/r7_cnn_train_regs.md)
+        u16x8 ae[MAXT], ao[MAXT], be, bo;
+        load(tab(lo), ae);
+        be = S.w2d[lo][lane];
+        u32x2 en = tab(lo + 1);
+        int ks = lo;
+        for (; ks + 2 < hi; ks += 2) {  // straight-line trips: k-steps ks (ae, be), ks + 1 (ao, bo)
+          u32x2 e = en;
+          en = tab(ks + 2);
+          load(e, ao);
+          bo = S.w2d[ks + 1][lane];
+#pragma unroll
+          for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ae[u], be, acc[u]);
+          e = en;
+          en = tab(ks + 3);
+          load(e, ae);
+          be = S.w2d[ks + 2][lane];
+#pragma unroll
+          for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ao[u], bo, acc[u]);
+        }
+        if (ks + 1 < hi) {  // two k-steps left, or one
+          load(en, ao);
+          bo = S.w2d[ks + 1][lane];
+#pragma unroll
+          for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ae[u], be, acc[u]);
+#pragma unroll
+          for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ao[u], bo, acc[u]);
+        } else {
+#pragma unroll
+          for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ae[u], be, acc[u]);
+        }
       }
+      // epilogue: the lane's 4 consecutive cells as e1 words (relu'(r1) from a1's dead mark), one 16-byte store
+      if (ci < C1) {
+#pragma unroll
+        for (int u = 0; u < MAXT; ++u) {
+          const int im = im0 + u;
+          u32x4 e;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const uint32_t am = (am4[u] >> (8 * r)) & 0xFFu;
+            e[r] = am == AM_DEAD ? 0u : static_cast<uint32_t>(f2bf(acc[u][r])) << (16 * (am & 1u));
+          }
+          *reinterpret_cast<u32x4*>(&e1[(im * C1 + ci) * EP + cell]) = e;
+        }
+      }
+    };
+    if constexpr (BREG) {  // straight-line passes: the fragment registers keep compile-time indices and live ranges
+      run_pass(0);
+      if (npass > 1) run_pass(1);
+    } else {
+      for (int pass = 0; pass < npass; ++pass) run_pass(pass);
     }
   }
   lds_sync();
@@ -1342,6 +1503,13 @@ bool cnn_fused_tail_enabled() {
   const char* e = std::getenv("PDE_CNN_FUSED_TAIL");
   return e != nullptr && e[0] == '1';
 }
+// PDE_CNN_P7B_FULLK=1 (diagnostic, read on every call): conv2's data gradient runs all KSD k-steps for every
+// tile class instead of the class's own range (p7b_ks_range) -- the skipped steps add exact zeros, so the two
+// must agree bit for bit.
+static bool cnn_p7b_fullk_enabled() {
+  const char* e = std::getenv("PDE_CNN_P7B_FULLK");
+  return e != nullptr && e[0] == '1';
+}
 int cnn_device_cus() {
   static int cus = 0;
   if (cus == 0) {
@@ -1416,7 +1584,8 @@ hipError_t cnn_train_fused(const float* images, const int64_t* tgt, int B, float
   static const int xmap_env = std::getenv("PDE_CNN_XMAP") ? std::atoi(std::getenv("PDE_CNN_XMAP")) : 0;
   static const int diag_frag = (std::getenv("PDE_CNN_DIAG_FRAG") ? 2 : 0) |  // timing only: see k_cnn_train
                                (std::getenv("PDE_CNN_DIAG_P9ST") ? 4 : 0);
-  const int xmap = (xmap_env != 0 && nwg % 8 == 0 ? 1 : 0) | diag_frag;
+  const int xmap = (xmap_env != 0 && nwg % 8 == 0 ? 1 : 0) | diag_frag |
+                   (cnn_p7b_fullk_enabled() ? XMAP_P7B_FULLK : 0);
   static const bool breg = std::getenv("PDE_CNN_BREG") != nullptr && std::getenv("PDE_CNN_BREG")[0] == '1';
   using TrainFn = decltype(&k_cnn_train<0, false>);
   static const TrainFn kTrain[2][4] = {
