@@ -11,6 +11,7 @@
 #include <cstring>
 #include <atomic>
 #include <mutex>
+#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -1210,6 +1211,47 @@ Tensor cnn_train(const Tensor& images, const Tensor& tgt, const Tensor& params, 
   return loss;
 }
 
+// Forward-only evaluation of the same network on the fused path (k_cnn_eval): (pred, logp), each an undefined
+// tensor when not asked for.  stats: a CnnEvalStats buffer (int64[4]) the batch's NLL sum / correct / count are
+// added to; it needs the labels.
+std::tuple<Tensor, Tensor> cnn_eval(const Tensor& images, const optional<Tensor>& tgt, const Tensor& params,
+                                    Tensor& frag, bool prep, bool want_pred, bool want_logp,
+                                    const optional<Tensor>& stats) {
+  CHECK_IN(images); CHECK_IN(params); CHECK_IN(frag);
+  CHECK_F32(images); CHECK_F32(params);
+  TORCH_CHECK(params.numel() == pde::cnn_num_params(), "cnn_eval: params must be the flat Net parameters");
+  TORCH_CHECK(images.numel() > 0 && images.numel() % (28 * 28) == 0, "cnn_eval: images must be [B,1,28,28]");
+  const int64_t B64 = images.numel() / (28 * 28);
+  TORCH_CHECK(B64 <= (1 << 30), "cnn_eval: batch too large");
+  const int B = static_cast<int>(B64);
+  TORCH_CHECK(frag.nbytes() >= pde::cnn_frag_bytes() && reinterpret_cast<uintptr_t>(frag.data_ptr()) % 16 == 0,
+              "cnn_eval: frag must be a 16-B aligned buffer of cnn_frag_bytes()");
+  const bool have_tgt = tgt.has_value() && tgt->defined();
+  if (have_tgt) {
+    CHECK_IN(*tgt);
+    TORCH_CHECK(tgt->scalar_type() == at::kLong, "cnn_eval: dtypes");
+    TORCH_CHECK(images.numel() == tgt->numel() * 28 * 28, "cnn_eval: images must be [B,1,28,28]");
+  }
+  const bool have_stats = stats.has_value() && stats->defined();
+  Tensor part;
+  if (have_stats) {
+    CHECK_IN(*stats);
+    TORCH_CHECK(have_tgt, "cnn_eval: stats need the labels");
+    TORCH_CHECK(stats->scalar_type() == at::kLong && stats->numel() == 4, "cnn_eval: stats must be int64[4]");
+    const int ni = pde::cnn_eval_images_per_workgroup();
+    part = at::empty({(B + ni - 1) / ni}, images.options());
+  }
+  Tensor pred, logp;
+  if (want_pred) pred = at::empty({B}, images.options().dtype(at::kLong));
+  if (want_logp) logp = at::empty({B, 10}, images.options());
+  check(pde::cnn_eval_fused(images.data_ptr<float>(), have_tgt ? tgt->data_ptr<int64_t>() : nullptr, B,
+                            params.data_ptr<float>(), frag.data_ptr(), want_logp ? logp.data_ptr<float>() : nullptr,
+                            want_pred ? pred.data_ptr<int64_t>() : nullptr, have_stats ? stats->data_ptr() : nullptr,
+                            have_stats ? part.data_ptr<float>() : nullptr, prep ? 1 : 0, cur_stream()),
+        "cnn_eval");
+  return std::make_tuple(pred, logp);
+}
+
 
 // Whole MLP training step in one persistent launch (mlp_fused.hip).  Per-layer lists (index l = layer); empty
 // tensors stand for absent state (mw / vw / mb / vb by mode, wtbf of layer 0, act / d of index 0).
@@ -1433,6 +1475,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return static_cast<int>(e);
         },
         py::arg("exec"));
+  m.def("cnn_eval", &cnn_eval, py::arg("images"), py::arg("tgt"), py::arg("params"), py::arg("frag"),
+        py::arg("prep"), py::arg("want_pred") = true, py::arg("want_logp") = false, py::arg("stats") = py::none());
+  m.def("cnn_eval_images_per_workgroup", &pde::cnn_eval_images_per_workgroup);
   m.def("cnn_frag_bytes", &pde::cnn_frag_bytes);
   m.def("cnn_num_params", &pde::cnn_num_params);
   m.def("cnn_smem_bytes", &pde::cnn_smem_bytes);

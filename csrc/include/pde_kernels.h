@@ -322,6 +322,17 @@ hipError_t cnn_train_fused(const float* images, const int64_t* tgt, int B, float
 int cnn_tail_error(int reset);
 hipError_t cnn_sgd_fused(float* params, const float* grads, const float* hp, void* frag, hipStream_t s,
                          int* step = nullptr);  // step: the optimiser's device step counter (+1 per call)
+// Forward-only evaluation of Net (eval mode: no dropout) on the training kernel's operands and precision: one
+// launch (two with prep = 1, which rebuilds the fragment image first), every activation in LDS.  Any B >= 1.
+// Each output is optional (nullptr skips it): logp [B,10] fp32 log-probabilities; pred [B] int64 argmax (the
+// lowest index wins a tie); stats, four 8-byte device words {double summed NLL, u64 correct, u64 images, u64
+// ticket} that the launch ADDS the batch to, deterministically (per-workgroup partials in loss_part, B /
+// cnn_eval_images_per_workgroup() rounded up floats, combined in workgroup order by the last workgroup to
+// arrive; the ticket must be 0 at launch and is left 0).  stats needs tgt and loss_part.  Reads neither the
+// dropout counter nor anything the training step writes except params / frag; writes only its outputs.
+int cnn_eval_images_per_workgroup();
+hipError_t cnn_eval_fused(const float* images, const int64_t* tgt, int B, const float* params, void* frag,
+                          float* logp, int64_t* pred, void* stats, float* loss_part, int prep, hipStream_t s);
 
 // dw (+)= EmbeddingBag-sum gradient; deterministic (row-owner scan) for tables with rows * L <= 2^26 and
 // D <= 256, fp32 atomics beyond

@@ -1493,6 +1493,294 @@ __device__ void cnn_fused_tail(const CnnTail& tl, int rb, f32x4* part, uint32_t*
                   tl.loss, tl.rng, tl.params, tl.hp, tl.frag, tl.step, one, 1.f);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Forward-only evaluation: k_cnn_train's P0-P4 in eval mode (no dropout), nothing else.  Same operands, same
+// precision and the same accumulation order in every stage, so a batch's summed NLL equals the training
+// kernel's eval-mode loss x B; the outputs are the log-probabilities, their argmax and running totals.
+//
+// Geometry: NI = 4 images per 16-wave workgroup, as in training.  The forward is the same chain of short
+// dependent phases, so it is latency-bound in the same way and 4 waves per image hide it; at the entry scripts'
+// test batch of 1024 images that is 256 workgroups, one per CU -- 8 images per workgroup would leave half the
+// chip idle for a pass that is one workgroup's latency long either way.  The LDS image is 69 KB (the training
+// kernel's 122 KB less everything the backward keeps): two workgroups would fit a CU's LDS, but a second
+// 16-wave workgroup needs 8 waves per SIMD, i.e. <= 64 VGPRs, and the kernel takes 72 (forcing 64 spills 8
+// registers to scratch) -- so larger batches run one workgroup per CU, in rounds.
+// ---------------------------------------------------------------------------------------------
+// max over a pooling window's 4 taps, by k_cnn_train's compare chain (the first tap wins a tie)
+__device__ __forceinline__ float pool4(const f32x4& v) {
+  float m = v[0];
+  if (v[1] > m) m = v[1];
+  if (v[2] > m) m = v[2];
+  if (v[3] > m) m = v[3];
+  return m;
+}
+
+struct CnnEvalSmem {
+  alignas(16) uint16_t r1n[NI][NC1][C1P];  // relu(maxpool(conv1)) channel-last (CnnSmem::r1n)
+  alignas(16) u16x8 w2f[KS2][2][64];       // conv2 B fragments; fc1's partials later (dead after conv2)
+  alignas(16) u16x8 w1f[64];               // conv1 B fragment
+  uint16_t x[NI][NXP];                     // images, rows of XP (CnnSmem::x / xpad / x1: same bank offsets)
+  uint16_t xpad[18];
+  uint16_t x1[NI][NXP];
+  alignas(16) float b1[C1];
+  alignas(16) float b2[C2];
+  alignas(16) float fc1b[F1];
+  alignas(16) float fc2w[FC2N];
+  alignas(16) float fc2b[F2];
+  alignas(16) float r2[NI][NIN];           // fc1 input; read as float4
+  float h1[NI][F1];
+  float lossim[NI];                        // -logp[y] per image (0 for an empty slot)
+  int hit[NI];                             // pred == y per image (0 for an empty slot)
+  int label[NI];
+};
+static_assert((offsetof(CnnEvalSmem, x1) - offsetof(CnnEvalSmem, x)) / 4 % 32 == 9,
+              "x1 bank offset from x (P1 gathers)");
+static_assert(offsetof(CnnEvalSmem, fc2b) == offsetof(CnnEvalSmem, fc2w) + sizeof(float) * FC2N, "fc2w, fc2b adjacent");
+static_assert(sizeof(float) * NI * F1 * FC1_KC <= sizeof(u16x8) * KS2 * 2 * 64, "fc1 partials alias w2f");
+static_assert(sizeof(CnnEvalSmem) <= 80 * 1024, "LDS budget");
+
+// The running totals of CnnEvalStats (models/cnn_fused.py): four 8-byte words.
+struct CnnEvalTotals {
+  double loss_sum;              // sum of -logp[y]
+  unsigned long long correct;   // predictions equal to the label
+  unsigned long long count;     // images
+  unsigned long long ticket;    // workgroups of the running launch that have arrived; 0 between launches
+};
+static_assert(sizeof(CnnEvalTotals) == 32, "CnnEvalStats holds int64[4]");
+
+__global__ __launch_bounds__(T) void k_cnn_eval(const float* __restrict__ images, const int64_t* __restrict__ tgt,
+                                                int B, const float* __restrict__ params,
+                                                const u16x8* __restrict__ frag, float* __restrict__ logp,
+                                                int64_t* __restrict__ pred, CnnEvalTotals* __restrict__ stats,
+                                                float* __restrict__ loss_part) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  CnnEvalSmem& S = *reinterpret_cast<CnnEvalSmem*>(smem_raw);
+  const int t = threadIdx.x;
+  const int lane = t & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int lr = lane & 15, lg = lane >> 4;
+  const float* gFC1W = params + O_FC1W;
+  const int n0 = blockIdx.x * NI;
+
+  // ---- P0: images -> bf16 (x, x1), conv1's fragment, the fp32 head weights; conv2's fragments are requested
+  // here and stored after conv1 (k_cnn_train's P0 without the backward's tables and the dropout masks).  Image
+  // addresses are clamped to the batch; an empty slot holds zeros.
+  const int qi = min(t, NI * NX / 4 - 1);
+  const int qim = (qi * 4) / NX, qoff = qi * 4 - qim * NX;
+  constexpr int NF2F = KS2 * 2 * 64, NF2D = KSD * 64;  // fragment image: [w2f | w2d | w1f]
+  u16x8 fr[2];
+  const u16x8 fw1 = frag[NF2F + NF2D + (t & 63)];
+  f32x4 img = *reinterpret_cast<const f32x4*>(images + static_cast<long>(min(n0 + qim, B - 1)) * NX + qoff);
+  if (t < NI * NX / 4) {
+    const int im = qim, off = qoff, n = n0 + im;
+    const f32x4 v = n < B ? img : f32x4{0.f, 0.f, 0.f, 0.f};
+    const int row = off / H0, col = off - row * H0;
+    uint16_t* dst = &S.x[im][row * XP + col];
+    const uint16_t b0 = f2bf(v[0]), b1 = f2bf(v[1]), b2 = f2bf(v[2]), b3 = f2bf(v[3]);
+    dst[0] = b0; dst[1] = b1; dst[2] = b2; dst[3] = b3;
+    uint16_t* d1 = &S.x1[im][row * XP + col];
+    if (col > 0) d1[-1] = b0;
+    d1[0] = b1; d1[1] = b2; d1[2] = b3;
+  }
+  for (int i = t; i < NI * H0 * (XP - H0 + 1); i += T) {  // zero columns: x 28.., x1 27..
+    const int r = i / (XP - H0 + 1), c = i - r * (XP - H0 + 1);
+    if (c > 0) (&S.x[0][0])[r * XP + H0 - 1 + c] = 0;
+    (&S.x1[0][0])[r * XP + H0 - 1 + c] = 0;
+  }
+  if (t < 64) S.w1f[t] = fw1;
+  for (int i = t; i < C1; i += T) S.b1[i] = params[O_B1 + i];
+  for (int i = t; i < C2; i += T) S.b2[i] = params[O_B2 + i];
+  for (int i = t; i < F1; i += T) S.fc1b[i] = params[O_FC1B + i];
+  for (int i = t; i < FC2N + F2; i += T) (&S.fc2w[0])[i] = params[O_FC2W + i];
+  if (t >= 384 && t < 384 + NI) {
+    const int im = t - 384;
+    S.label[im] = (tgt != nullptr && n0 + im < B) ? static_cast<int>(tgt[n0 + im]) : 0;
+  }
+  fr[0] = frag[t];
+  fr[1] = frag[min(t + T, NF2F - 1)];
+  lds_sync();
+
+  // ---- P1: conv1 + maxpool2 + relu on the accumulators (k_cnn_train's P1; only the channel-last r1n is kept)
+  {
+    int koff[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int k = lg * 8 + 2 * p;
+      koff[p] = k < KS * 6 ? (k / 6) * XP + (k % 6) : 0;
+    }
+    const u16x8 bw = S.w1f[lane];
+    const int tap = lr & 3, dy = tap >> 1, dx = tap & 1;
+    const uint16_t* xsrc = dx ? &S.x1[0][0] - 1 : &S.x[0][0];
+    const uint16_t* xlane = xsrc + dy * XP + 2 * (lr >> 2) + dx;
+    auto gather = [&](int tile, u16x8& a) {
+      const int im = tile / MT1, t4 = tile - im * MT1, py = t4 / (P1 / 4), px0 = (t4 - py * (P1 / 4)) * 4;
+      const uint16_t* xb = xlane + im * NXP + 2 * py * XP + 2 * px0;
+      u32x4 v;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) v[p] = *reinterpret_cast<const uint32_t*>(xb + koff[p]);
+      a = __builtin_bit_cast(u16x8, v);
+    };
+    constexpr int NT1 = NI * MT1 / NW;  // 9 tiles per wave
+    u16x8 ag[NT1];
+#pragma unroll
+    for (int u = 0; u < NT1; ++u) gather(wid + u * NW, ag[u]);
+    f32x4 accs[NT1];
+#pragma unroll
+    for (int u = 0; u < NT1; ++u) accs[u] = mfma(ag[u], bw, f32x4{0.f, 0.f, 0.f, 0.f});
+    const float bias1 = lr < C1 ? S.b1[lr] : 0.f;
+#pragma unroll
+    for (int u = 0; u < NT1; ++u) {
+      const int tile = wid + u * NW;
+      const int im = tile / MT1, c0 = (tile - im * MT1) * 4;
+      const f32x4 acc = accs[u];
+      const float m = pool4(acc);
+      // lanes co >= C1: w1f's columns and bias1 are zero there, so r1n's ci padding gets its zeros
+      S.r1n[im][c0 + lg][lr] = f2bf(fmaxf(m + bias1, 0.f));
+    }
+  }
+  {
+    u16x8* dst = &S.w2f[0][0][0];
+    dst[t] = fr[0];
+    if (t + T < NF2F) dst[t + T] = fr[1];
+  }
+  lds_sync();
+
+  // fc1's weights for P3, requested now: their L2 latency hides under conv2
+  f32x4 w3[8];
+  if (t < F1 * FC1_KC) {
+    const int j = t / FC1_KC, kc = t - j * FC1_KC;
+    const f32x4* w4 = reinterpret_cast<const f32x4*>(gFC1W + j * NIN + kc * 4);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) w3[q] = w4[q * (FC1_KC)];
+  }
+
+  // ---- P2: conv2 (k-steps ascending) + bias + maxpool2 + relu on the accumulators (k_cnn_train's P2)
+  for (int mtile = wid; mtile < NI * 4; mtile += NW) {
+    const int im = mtile >> 2, mt = mtile & 3;
+    const int tap = lr & 3, dy = tap >> 1, dx = tap & 1;
+    const int cell = mt * 4 + (lr >> 2), py = cell >> 2, px = cell & 3;
+    const int rb = (2 * py + dy) * P1 + 2 * px + dx;
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+    const uint16_t* r1n = &S.r1n[im][0][(lg & 1) * 8];
+#pragma unroll
+    for (int ks = 0; ks < KS2; ++ks) {
+      const int tp = 2 * ks + (lg >> 1), ky = tp / KS, kx = tp - ky * KS;
+      const u16x8 a = tp < KS * KS ? *reinterpret_cast<const u16x8*>(r1n + (rb + ky * P1 + kx) * C1P)
+                                   : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      acc0 = mfma(a, S.w2f[ks][0][lane], acc0);
+      acc1 = mfma(a, S.w2f[ks][1][lane], acc1);
+    }
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      const int co = nt * 16 + lr;
+      if (co < C2) {
+        const f32x4 v = nt == 0 ? acc0 : acc1;
+        const float m = pool4(v);
+        S.r2[im][co * NC2 + mt * 4 + lg] = fmaxf(m + S.b2[co], 0.f);
+      }
+    }
+  }
+  lds_sync();
+
+  // ---- P3: fc1 + relu (k_cnn_train's P3: partials [kc][im][j] summed in kc order)
+  {
+    float* part = reinterpret_cast<float*>(&S.w2f[0][0][0]);
+    if (t < F1 * FC1_KC) {
+      const int j = t / FC1_KC, kc = t - j * FC1_KC;
+      float s4[NI] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+#pragma unroll
+        for (int im = 0; im < NI; ++im) {
+          const f32x4 x = *reinterpret_cast<const f32x4*>(&S.r2[im][q * 4 * FC1_KC + kc * 4]);
+          s4[im] += w3[q][0] * x[0] + w3[q][1] * x[1] + w3[q][2] * x[2] + w3[q][3] * x[3];
+        }
+#pragma unroll
+      for (int im = 0; im < NI; ++im) part[(kc * NI + im) * F1 + j] = s4[im];
+    }
+    lds_sync();
+    if (t < NI * F1) {
+      const int im = t / F1, j = t - im * F1;
+      float s1 = S.fc1b[j];
+#pragma unroll
+      for (int kc = 0; kc < FC1_KC; ++kc) s1 += part[(kc * NI + im) * F1 + j];
+      S.h1[im][j] = fmaxf(s1, 0.f);
+    }
+  }
+  lds_sync();
+
+  // ---- P4: fc2 + log_softmax, one wave per image (k_cnn_train's P4), then the outputs: the 10
+  // log-probabilities, their argmax (lowest index on a tie) and the image's NLL / hit for the totals
+  if (wid < NI) {
+    const int im = wid, v = lane >> 2, p = lane & 3;
+    const bool lv = v < F2;
+    const int vr = lv ? v : 0;
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < (F1 + 3) / 4; ++k) {
+      const int j = p + 4 * k;
+      if (j < F1) s += S.fc2w[vr * F1 + j] * S.h1[im][j];
+    }
+    s += dppf<DPP_XOR1>(s);
+    s += dppf<DPP_XOR2>(s);
+    const float logit = s + S.fc2b[vr];
+    const float m = wave_max_dpp(lv ? logit : -INFINITY);
+    const float ex = __expf(logit - m);
+    const float se = wave_sum_dpp(lv && p == 0 ? ex : 0.f);
+    const float lse = m + __logf(se);
+    const int y = S.label[im];
+    const float ly = lanef(logit, __builtin_amdgcn_readfirstlane(4 * y));
+    const float lp = logit - lse;
+    const float best = wave_max_dpp(lv ? lp : -INFINITY);
+    const float cand = (lv && lp == best) ? static_cast<float>(v) : static_cast<float>(F2);
+    const int am = static_cast<int>(wave_all(cand, [](float a, float b) { return fminf(a, b); }));
+    const int pr = am < F2 ? am : 0;  // (no lane equals the maximum only when the logits are NaN)
+    const int n = n0 + im;            // wave-uniform
+    const bool ok = n < B;
+    if (ok && logp != nullptr && lv && p == 0) logp[static_cast<long>(n) * F2 + v] = lp;
+    if (lane == 0) {
+      if (ok && pred != nullptr) pred[n] = pr;
+      S.lossim[im] = ok ? lse - ly : 0.f;  // == -logp[y]
+      S.hit[im] = (ok && pr == y) ? 1 : 0;
+    }
+  }
+  if (stats == nullptr) return;
+  lds_sync();
+
+  // ---- totals.  Every workgroup publishes its images' NLL sum and adds its hits (integer atomic); the
+  // last one to draw a ticket sums the partials in workgroup order -- the same value whatever order the
+  // workgroups finished in -- adds it to the running total and resets the ticket for the next launch or replay.
+  if (wid == 0) {
+    const float l = wave_sum_dpp(lane < NI ? S.lossim[lane] : 0.f);
+    unsigned long long old = 0;
+    if (lane == 0) {
+      const int h = S.hit[0] + S.hit[1] + S.hit[2] + S.hit[3];
+      __hip_atomic_store(&loss_part[blockIdx.x], l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (h != 0)
+        __hip_atomic_fetch_add(&stats->correct, static_cast<unsigned long long>(h), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      old = __hip_atomic_fetch_add(&stats->ticket, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    const unsigned last = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(old));
+    if (last == gridDim.x - 1) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      float sum = 0.f;
+      for (int b = lane; b < static_cast<int>(gridDim.x); b += 64)
+        sum += __hip_atomic_load(&loss_part[b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      sum = wave_sum(sum);
+      if (lane == 0) {
+        stats->loss_sum += static_cast<double>(sum);
+        stats->count += static_cast<unsigned long long>(B);
+        __hip_atomic_store(&stats->ticket, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 int cnn_num_params() { return NPARAM; }
@@ -1626,6 +1914,27 @@ hipError_t cnn_train_fused(const float* images, const int64_t* tgt, int B, float
                        accumulate, loss_part, B, loss, rng, params, (diag & 16) ? nullptr : sgd_hp,
                        static_cast<uint16_t*>(frag), sgd_step, view, xscale, rb0);
   }
+  return hipGetLastError();
+}
+
+int cnn_eval_images_per_workgroup() { return NI; }
+
+hipError_t cnn_eval_fused(const float* images, const int64_t* tgt, int B, const float* params, void* frag,
+                          float* logp, int64_t* pred, void* stats, float* loss_part, int prep, hipStream_t s) {
+  if (B < 1 || (reinterpret_cast<uintptr_t>(frag) & 15) || (reinterpret_cast<uintptr_t>(stats) & 7))
+    return hipErrorInvalidValue;
+  if (stats != nullptr && (tgt == nullptr || loss_part == nullptr)) return hipErrorInvalidValue;
+  const size_t sm = sizeof(CnnEvalSmem);
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cnn_eval), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              static_cast<int>(sm));
+    attr = true;
+  }
+  if (prep)
+    hipLaunchKernelGGL(k_cnn_prep, dim3(ceil_div(NFRAG, 256)), dim3(256), 0, s, params, static_cast<u16x8*>(frag));
+  hipLaunchKernelGGL(k_cnn_eval, dim3(ceil_div(B, NI)), dim3(T), sm, s, images, tgt, B, params,
+                     static_cast<const u16x8*>(frag), logp, pred, static_cast<CnnEvalTotals*>(stats), loss_part);
   return hipGetLastError();
 }
 

@@ -257,14 +257,27 @@ class Trainer:
         # The reference never calls model.eval() (:117-130); we evaluate in eval mode (dropout off).
         was = self.model.training
         self.model.eval()
-        correct = torch.zeros((), dtype=torch.long, device=self.ctx.device)
         total = 0
-        for images, labels in self.test_data:
-            outputs = self.model(images)
-            predicted = outputs.float().argmax(1)
-            total += labels.size(0)
-            correct += (predicted == labels).sum()
-        c = int(correct.item())
+        use_fused = self.fused is not None
+        if use_fused:
+            from ..models.cnn_fused import CnnEvalStats, fused_eval_enabled
+
+            use_fused = fused_eval_enabled()  # PDE_CNN_EVAL=0: the layer pass, for A/B runs
+        if use_fused:
+            # the fused forward kernel: one launch per batch, the counts stay on the device until the pass ends
+            stats = CnnEvalStats(self.ctx.device)
+            for images, labels in self.test_data:
+                self.fused.evaluate(images, labels, stats)
+                total += labels.size(0)
+            c = stats.result()[1]
+        else:
+            correct = torch.zeros((), dtype=torch.long, device=self.ctx.device)
+            for images, labels in self.test_data:
+                outputs = self.model(images)
+                predicted = outputs.float().argmax(1)
+                total += labels.size(0)
+                correct += (predicted == labels).sum()
+            c = int(correct.item())
         self.log.print(f"Test accuracy: {(c / max(1, total)) * 100:.2f}%", all_ranks=True)
         gc = pdist.sum_over_ranks(c, self.ctx.device)
         gt = pdist.sum_over_ranks(total, self.ctx.device)

@@ -111,10 +111,22 @@ def main(argv=None):
         model.eval()
         loader = ShardedLoader(test_set, args.batch_size, 1, 0, shuffle=False)
         correct = total = 0
-        for images, labels in loader:
-            predicted = model(images).float().argmax(1)
-            total += labels.size(0)
-            correct += int((predicted == labels).sum().item())
+        use_fused = fused_step is not None
+        if use_fused:
+            from ..models.cnn_fused import CnnEvalStats, fused_eval_enabled
+
+            use_fused = fused_eval_enabled()  # PDE_CNN_EVAL=0: the layer pass, for A/B runs
+        if use_fused:  # the fused forward kernel; the counts stay on the device until the pass ends
+            stats = CnnEvalStats(dev)
+            for images, labels in loader:
+                fused_step.fused.evaluate(images, labels, stats)
+                total += labels.size(0)
+            correct = stats.result()[1]
+        else:
+            for images, labels in loader:
+                predicted = model(images).float().argmax(1)
+                total += labels.size(0)
+                correct += int((predicted == labels).sum().item())
         print(f"Accuracy: {(correct / total) * 100:.2f}%", flush=True)
 
     state = hvd.elastic.TorchState(model, optimizer, batch=0, epoch=0)

@@ -562,15 +562,29 @@ def run_elastic(args):
 
 
 @torch.no_grad()
-def _test(model, loader, dev, comm, log):
+def _test(model, loader, dev, comm, log, fused=None):
+    """``fused``: the model's FusedCNN -- the pass runs through its forward kernel (PDE_CNN_EVAL=0: layer pass)."""
     was = model.training
     model.eval()
-    correct = torch.zeros((), dtype=torch.long, device=dev)
     total = 0
-    for images, labels in loader:
-        correct += (model(images).float().argmax(1) == labels).sum()
-        total += labels.size(0)
-    t = torch.tensor([float(correct.item()), float(total)])
+    if fused is not None:
+        from ..models.cnn_fused import CnnEvalStats, fused_eval_enabled
+
+        if not fused_eval_enabled():
+            fused = None
+    if fused is not None:
+        stats = CnnEvalStats(dev)
+        for images, labels in loader:
+            fused.evaluate(images, labels, stats)
+            total += labels.size(0)
+        correct = stats.result()[1]
+    else:
+        count = torch.zeros((), dtype=torch.long, device=dev)
+        for images, labels in loader:
+            count += (model(images).float().argmax(1) == labels).sum()
+            total += labels.size(0)
+        correct = count.item()
+    t = torch.tensor([float(correct), float(total)])
     if comm.size > 1:
         try:
             dist.all_reduce(t)
@@ -947,7 +961,7 @@ def run_elastic_fused(args, report=None):
                     dcommit.save_sync()
                 else:
                     commit.save()
-                _test(model, test_data, dev, comm, log)
+                _test(model, test_data, dev, comm, log, fused=fused)
                 if rank == 0 and save_every and snapshot_path and epoch % save_every == 0:
                     save_snapshot(snapshot_path, model.state_dict(), epoch, opt.state_dict())
                     log.print(f"Epoch {epoch} | Training snapshot saved at {snapshot_path}")

@@ -33,8 +33,18 @@ gradients, identical on every rank, and the SGD update stays fused -- the all-re
 The fragment image is re-derived (prep launch) whenever anything other than these fused updates may have
 written the weights: any other optimiser step bumps the weight generation (:func:`.functional.
 bump_weight_generation`); direct writes (``load_state_dict``, broadcasts) must call :meth:`invalidate`.
+
+Evaluation runs on the same path (``k_cnn_eval``: the training kernel's forward, eval mode, one launch)::
+
+    pred = fused.predict(x)                          # int64 [B]; logprobs=True: (pred, logp [B, 10])
+    stats = CnnEvalStats(dev)
+    for x, y in test_loader:
+        fused.evaluate(x, y, stats)                  # no host synchronisation
+    loss_sum, correct, count = stats.result()        # one device-to-host copy per pass
 """
 from __future__ import annotations
+
+import os
 
 import torch
 
@@ -183,3 +193,59 @@ class FusedCNN:
             # the weights did not change: the image stays current until someone writes them
             self._frag_gen = OF.weight_generation()
         return loss
+
+    # ---- forward-only evaluation (k_cnn_eval): eval mode whatever net.training says ---------------------------
+    def _eval(self, x, y, stats, want_pred, want_logp):
+        x = x.float().contiguous()
+        if y is not None:
+            y = y.long().contiguous()
+        # the fragment-currency rule of forward_backward; the weights do not change, so the generation stays
+        prep = self.always_prep or self._frag_gen is None or self._frag_gen != OF.weight_generation()
+        pred, logp = _native.C().cnn_eval(x, y, self.flat, self.frag, prep, want_pred, want_logp,
+                                          None if stats is None else stats.buf)
+        self._frag_gen = OF.weight_generation()
+        return pred, logp
+
+    @torch.no_grad()
+    def predict(self, x: torch.Tensor, logprobs: bool = False):
+        """Predicted class of every image (int64 ``[B]``, lowest index on a tie) on the fused path; with
+        ``logprobs`` also the fp32 ``[B, 10]`` log-probabilities: ``(pred, logp)``."""
+        pred, logp = self._eval(x, None, None, True, logprobs)
+        return (pred, logp) if logprobs else pred
+
+    @torch.no_grad()
+    def evaluate(self, x: torch.Tensor, y: torch.Tensor, stats: "CnnEvalStats | None" = None,
+                 logprobs: bool = False):
+        """Add the batch's summed NLL, correct predictions and image count to ``stats`` (a new
+        :class:`CnnEvalStats` when ``None``) without any host synchronisation; returns ``stats``, or
+        ``(stats, logp)`` with ``logprobs``.  Read the totals once per pass with ``stats.result()``."""
+        if stats is None:
+            stats = CnnEvalStats(self.flat.device)
+        _, logp = self._eval(x, y, stats, False, logprobs)
+        return (stats, logp) if logprobs else stats
+
+
+def fused_eval_enabled() -> bool:
+    """The entry scripts' test passes run through :meth:`FusedCNN.evaluate`; ``PDE_CNN_EVAL=0`` keeps the
+    layer-by-layer pass (A/B runs)."""
+    return os.environ.get("PDE_CNN_EVAL", "1") != "0"
+
+
+class CnnEvalStats:
+    """Running totals of :meth:`FusedCNN.evaluate` on the device: summed NLL (float64), correct predictions and
+    images.  The sum over a batch is combined in a fixed order, so equal calls give bitwise-equal totals.  Calls that
+    share one buffer must be ordered on the device (one stream, or one captured graph): a launch owns the arrival
+    ticket in the buffer until it ends."""
+
+    def __init__(self, device):
+        # {loss_sum as float64 bits, correct, count, the kernel's arrival ticket (0 between launches)}
+        self.buf = torch.zeros(4, dtype=torch.int64, device=device)
+
+    def zero_(self):
+        self.buf.zero_()
+        return self
+
+    def result(self):
+        """``(loss_sum, correct, count)`` -- one device-to-host copy."""
+        host = self.buf.cpu()
+        return float(host[:1].view(torch.float64).item()), int(host[1].item()), int(host[2].item())
