@@ -401,6 +401,114 @@ __device__ __forceinline__ void out_st4(float* p, f32x4 v) {
   else *reinterpret_cast<f32x4*>(p) = v;
 }
 
+// ---- P0 of k_cnn_train (TRAIN) and k_cnn_eval: images -> bf16 (x, x1), conv1's fragment, the fp32 head
+// weights, the labels; TRAIN also the backward's constant tables and the dropout masks.
+// ONE round trip: every value the phase takes from memory is requested before the first wait and the first
+// LDS store -- conv1's fragment, the image quad, one head parameter per thread over the flat range
+// [b1 | b2 | fc1b fc2w fc2b], rng[0] (a vector load: a scalar one would be a second trip behind the kernel
+// arguments' wait) and the labels -- all unconditional, from clamped addresses; only the LDS stores are
+// predicated (a load under `if (t < N)` becomes an exec branch with its own vmcnt(0): one dependent trip
+// each).  conv2's forward fragments (fr, stored after conv1) are requested last: vmcnt retires in issue
+// order, so P0's own waits are counted ones that leave them in flight.  The LDS fills that need no load run
+// while the requests are out.  Image addresses are clamped to the batch; an empty slot holds zeros.
+template <bool TRAIN, class Smem>
+__device__ __forceinline__ void cnn_p0(Smem& S, int t, int n0, int B, const float* __restrict__ images,
+                                       const int64_t* __restrict__ tgt, const float* __restrict__ params,
+                                       const u16x8* __restrict__ frag, const unsigned long long* __restrict__ rng,
+                                       float p_drop2, float p_drop1, int training, u16x8 (&fr)[2]) {
+  static_assert(NI * NX / 4 <= T, "one image quad per thread");
+  constexpr int NF2F = KS2 * 2 * 64, NF2D = KSD * 64;  // fragment image: [w2f | w2d | w1f]
+  static_assert(NF2F <= 2 * T && NF2F + NF2D + 64 == NFRAG, "fragment slots");
+  constexpr int NH = C1 + C2 + F1 + FC2N + F2;  // 590 head parameters, one per thread
+  static_assert(NH <= T && O_FC2W == O_FC1B + F1 && O_FC2B == O_FC2W + FC2N, "fc1b, fc2w, fc2b contiguous");
+  static_assert((NI & (NI - 1)) == 0 && 384 % NI == 0, "label threads 384..: slot t & (NI - 1)");
+  const int qi = min(t, NI * NX / 4 - 1);
+  const int qim = (qi * 4) / NX, qoff = qi * 4 - qim * NX;
+  const int hi = min(t, NH - 1);
+  const int hsrc = hi < C1 ? O_B1 + hi : hi < C1 + C2 ? O_B2 + hi - C1 : O_FC1B + hi - (C1 + C2);
+  const int lslot = t & (NI - 1);
+  // the label address is selected, never the loaded value (tgt may be null in k_cnn_eval: any valid address)
+  const int64_t* lbase = tgt != nullptr ? tgt : reinterpret_cast<const int64_t*>(frag);
+  const int lidx = tgt != nullptr ? min(n0 + lslot, B - 1) : 0;
+  // rng[0] through a per-lane offset the compiler cannot prove uniform: a global (vector) load
+  int rofs = 0;
+  asm("" : "+v"(rofs));
+  // requests
+  const u16x8 fw1 = frag[NF2F + NF2D + (t & 63)];
+  const f32x4 img = *reinterpret_cast<const f32x4*>(images + static_cast<long>(min(n0 + qim, B - 1)) * NX + qoff);
+  const float hv = params[hsrc];
+  unsigned long long r0 = 0;
+  if constexpr (TRAIN) r0 = rng[rofs];
+  // (the int64 label's low word: what static_cast<int> keeps -- no half-dead register pair for the allocator
+  // to reuse while the load is in flight, which costs a wait right here)
+  const int lab = reinterpret_cast<const int*>(lbase)[2 * lidx];
+  fr[0] = frag[t];
+  fr[1] = frag[min(t + T, NF2F - 1)];
+  // fills that need no load
+  static_assert(H0 % 4 == 0 && XP >= H0 + 6, "image quads within a row; kx = 5 reads stay in the row");
+  for (int i = t; i < NI * H0 * (XP - H0 + 1); i += T) {  // zero columns: x 28.., x1 27..
+    const int r = i / (XP - H0 + 1), c = i - r * (XP - H0 + 1);
+    if (c > 0) (&S.x[0][0])[r * XP + H0 - 1 + c] = 0;
+    (&S.x1[0][0])[r * XP + H0 - 1 + c] = 0;
+  }
+  if constexpr (TRAIN) {
+    for (int i = t; i < NI * O2 * O2; i += T) {  // co group 2 zeroed (co 20..23 stay zero; 16..19 rewritten per step)
+      const int im = i / (O2 * O2), pos = i - im * (O2 * O2);
+      *reinterpret_cast<u16x8*>(&S.d2n[d2n_ofs(im, pos / O2, pos % O2, 16)]) = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    if (t < 8) S.zero16[t] = 0;
+    static_assert((NI * NXP) % 8 == 0 && NI * NXP / 8 <= T, "xone: one 16-byte store per thread");
+    if (t < NI * NXP / 8)
+      reinterpret_cast<u16x8*>(&S.xone[0][0])[t] =
+          u16x8{0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
+    if (t < KSD * 4) {  // P7b's per-k-group tap table (groups past NGD never match: ky = kx = 0x8000)
+      const int g = t, tap = g / CG, cg = g - tap * CG, ky = tap / KS, kx = tap - ky * KS;
+      S.p7tab[g][0] = g < NGD ? (static_cast<uint32_t>(ky) << 16) | static_cast<uint32_t>(kx) : 0x80008000u;
+      S.p7tab[g][1] = static_cast<uint32_t>(g < NGD ? (-(ky * D2N_RP + kx * D2N_P) + cg * D2N_Q) * 2 : 0);  // bytes
+    }
+  }
+  // consumers, in request order
+  if (t < 64) S.w1f[t] = fw1;
+  if (t < NI * NX / 4) {
+    const int im = qim, off = qoff, n = n0 + im;
+    const f32x4 v = n < B ? img : f32x4{0.f, 0.f, 0.f, 0.f};
+    const int row = off / H0, col = off - row * H0;  // a quad never crosses a row (H0 % 4 == 0)
+    uint16_t* dst = &S.x[im][row * XP + col];
+    const uint16_t b0 = f2bf(v[0]), b1 = f2bf(v[1]), b2 = f2bf(v[2]), b3 = f2bf(v[3]);
+    dst[0] = b0; dst[1] = b1; dst[2] = b2; dst[3] = b3;
+    uint16_t* d1 = &S.x1[im][row * XP + col];
+    if (col > 0) d1[-1] = b0;
+    d1[0] = b1; d1[1] = b2; d1[2] = b3;
+  }
+  if (t < NH) {  // fc2w and fc2b are adjacent in LDS as in params
+    // (a byte offset, not a pointer select: that one becomes a branch per destination array)
+    const int hofs = hi < C1             ? static_cast<int>(offsetof(Smem, b1)) + 4 * hi
+                     : hi < C1 + C2      ? static_cast<int>(offsetof(Smem, b2)) + 4 * (hi - C1)
+                     : hi < C1 + C2 + F1 ? static_cast<int>(offsetof(Smem, fc1b)) + 4 * (hi - (C1 + C2))
+                                         : static_cast<int>(offsetof(Smem, fc2w)) + 4 * (hi - (C1 + C2 + F1));
+    *reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(&S) + hofs) = hv;
+  }
+  if constexpr (TRAIN) {
+    const unsigned long long seed = r0 * 0xD1B54A32D192ED03ULL;
+    const float keep2 = training ? 1.f / (1.f - p_drop2) : 1.f;
+    const float keep1 = training ? 1.f / (1.f - p_drop1) : 1.f;
+    if (t < NI * C2) {
+      const int im = t / C2, c = t - im * C2;
+      const unsigned long long id = static_cast<unsigned long long>(n0 + im) * C2 + c;
+      S.mc2[im][c] = (!training || hash_u01(seed ^ 0x5bd1e995ULL, id) >= p_drop2) ? keep2 : 0.f;
+    } else if (t >= 128 && t < 128 + NI * F1) {
+      const int u = t - 128, im = u / F1, j = u - im * F1;
+      const unsigned long long id = static_cast<unsigned long long>(n0 + im) * F1 + j;
+      S.m1[im][j] = (!training || hash_u01(seed ^ 0x27d4eb2fULL, id) >= p_drop1) ? keep1 : 0.f;
+    }
+  }
+  if (t >= 384 && t < 384 + NI) {
+    const bool ok = tgt != nullptr && n0 + lslot < B;
+    if constexpr (TRAIN) S.valid[lslot] = ok ? 1.f : 0.f;
+    S.label[lslot] = ok ? static_cast<int>(lab) : 0;
+  }
+}
+
 // BREG: P7b's B operand (the conv2 data-gradient fragments, identical for every wave) is loaded from the
 // fragment image into registers at the start of P7a instead of being staged in LDS -- a quarter of P7b's LDS
 // traffic moves to the vector-memory path (L1 / L2 hits), which runs beside the LDS.
@@ -418,6 +526,11 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
 #define PDE_STAMP(k)                                                                      \
   if (stamps != nullptr && threadIdx.x == 0) stamps[blockIdx.x * 16 + (k)] = wall_clock64(); \
   if (stop_after == (k)) return
+  // every argument P0 and the stamps read is live here: the kernel-argument segment arrives behind ONE wait
+  // (left to the compiler, stamps / stop_after / xmap / frag each cost P0 a scalar round trip of their own)
+  asm volatile("" ::"s"(images), "s"(tgt), "s"(B), "s"(params), "s"(frag), "s"(rng), "s"(p_drop2), "s"(p_drop1),
+               "s"(training), "s"(slabs), "s"(loss_part), "s"(acts), "s"(stamps), "s"(stop_after), "s"(xmap),
+               "s"(tail.accumulate), "s"(tail.B), "s"(tail.on), "s"(gridDim.x));
   PDE_STAMP(0);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   CnnSmem& S = *reinterpret_cast<CnnSmem*>(smem_raw);
@@ -428,83 +541,22 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
   const float* gW1 = params + O_W1;
   const float* gW2 = params + O_W2;
   const float* gFC1W = params + O_FC1W;
-  const float* gFC1B = params + O_FC1B;
   // xmap: workgroups that share an XCD (blockIdx % 8 under the observed round-robin placement) take
   // consecutive images, so the 8 workgroups writing one 128-B line of an activation row sit behind one L2
   const int lwg = (xmap & 1) ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
   const int n0 = lwg * NI;
 
-  // ---- P0: images -> bf16, weights -> bf16 MFMA fragments, fp32 head weights, dropout masks ------
-  // every global load of the phase is issued first (unconditional, clamped addresses): conv1's fragment (w1f),
-  // then the image quad.  Only w1f is stored to LDS now; conv2's forward fragments (w2f) are requested at the
-  // end of P0 and stored at the end of P1, its data-gradient fragments (w2d) are requested in P4 and stored at
-  // the end of P6 -- their latency is on no phase's critical path, and the burst of fragment reads every
-  // workgroup makes at the start is 28 KB instead of 47 KB.
-  // (vmcnt retires loads in issue order: the loads P0 itself consumes -- w1f, images, the head parameters --
-  // are issued before the deferred fragment loads)
-  static_assert(NI * NX / 4 <= T, "one image quad per thread");
-  const int qi = min(t, NI * NX / 4 - 1);
-  const int qim = (qi * 4) / NX, qoff = qi * 4 - qim * NX;
+  // ---- P0 (cnn_p0): images -> bf16, conv1's bf16 MFMA fragment, fp32 head weights, dropout masks, tables.
+  // Only w1f is stored to LDS now; conv2's forward fragments (w2f, fr) are requested in P0 and stored at the
+  // end of P1, its data-gradient fragments (w2d) are requested in P4 and stored at the end of P6 -- their
+  // latency is on no phase's critical path, and the burst of fragment reads every workgroup makes at the
+  // start is 28 KB instead of 47 KB.
   constexpr int NF2F = KS2 * 2 * 64, NF2D = KSD * 64;  // fragment image: [w2f | w2d | w1f]
   static_assert(NF2F <= 2 * T && NF2D <= 2 * T && NF2F + NF2D + 64 == NFRAG, "fragment slots");
-  u16x8 fr[2];
-  const u16x8 fw1 = frag[NF2F + NF2D + (t & 63)];
-  f32x4 img = *reinterpret_cast<const f32x4*>(images + static_cast<long>(min(n0 + qim, B - 1)) * NX + qoff);
-  if (t < NI * NX / 4) {
-    const int im = qim, off = qoff, n = n0 + im;
-    const f32x4 v = n < B ? img : f32x4{0.f, 0.f, 0.f, 0.f};
-    const int row = off / H0, col = off - row * H0;  // a quad never crosses a row (H0 % 4 == 0)
-    uint16_t* dst = &S.x[im][row * XP + col];
-    const uint16_t b0 = f2bf(v[0]), b1 = f2bf(v[1]), b2 = f2bf(v[2]), b3 = f2bf(v[3]);
-    dst[0] = b0; dst[1] = b1; dst[2] = b2; dst[3] = b3;
-    uint16_t* d1 = &S.x1[im][row * XP + col];
-    if (col > 0) d1[-1] = b0;
-    d1[0] = b1; d1[1] = b2; d1[2] = b3;
-  }
-  static_assert(H0 % 4 == 0 && XP >= H0 + 6, "image quads within a row; kx = 5 reads stay in the row");
-  for (int i = t; i < NI * H0 * (XP - H0 + 1); i += T) {  // zero columns: x 28.., x1 27..
-    const int r = i / (XP - H0 + 1), c = i - r * (XP - H0 + 1);
-    if (c > 0) (&S.x[0][0])[r * XP + H0 - 1 + c] = 0;
-    (&S.x1[0][0])[r * XP + H0 - 1 + c] = 0;
-  }
-  if (t < 64) S.w1f[t] = fw1;
-  for (int i = t; i < NI * O2 * O2; i += T) {  // co group 2 zeroed (co 20..23 stay zero; 16..19 rewritten per step)
-    const int im = i / (O2 * O2), pos = i - im * (O2 * O2);
-    *reinterpret_cast<u16x8*>(&S.d2n[d2n_ofs(im, pos / O2, pos % O2, 16)]) = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-  }
-  if (t < 8) S.zero16[t] = 0;
-  static_assert((NI * NXP) % 8 == 0 && NI * NXP / 8 <= T, "xone: one 16-byte store per thread");
-  if (t < NI * NXP / 8)
-    reinterpret_cast<u16x8*>(&S.xone[0][0])[t] = u16x8{0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
-  if (t < KSD * 4) {  // P7b's per-k-group tap table (groups past NGD never match: ky = kx = 0x8000)
-    const int g = t, tap = g / CG, cg = g - tap * CG, ky = tap / KS, kx = tap - ky * KS;
-    S.p7tab[g][0] = g < NGD ? (static_cast<uint32_t>(ky) << 16) | static_cast<uint32_t>(kx) : 0x80008000u;
-    S.p7tab[g][1] = static_cast<uint32_t>(g < NGD ? (-(ky * D2N_RP + kx * D2N_P) + cg * D2N_Q) * 2 : 0);  // bytes
-  }
-  for (int i = t; i < C1; i += T) S.b1[i] = params[O_B1 + i];
-  for (int i = t; i < C2; i += T) S.b2[i] = params[O_B2 + i];
-  for (int i = t; i < F1; i += T) S.fc1b[i] = gFC1B[i];
-  for (int i = t; i < FC2N + F2; i += T) (&S.fc2w[0])[i] = params[O_FC2W + i];
-  const unsigned long long seed = rng[0] * 0xD1B54A32D192ED03ULL;
-  const float keep2 = training ? 1.f / (1.f - p_drop2) : 1.f;
-  const float keep1 = training ? 1.f / (1.f - p_drop1) : 1.f;
-  if (t < NI * C2) {
-    const int im = t / C2, c = t - im * C2;
-    const unsigned long long id = static_cast<unsigned long long>(n0 + im) * C2 + c;
-    S.mc2[im][c] = (!training || hash_u01(seed ^ 0x5bd1e995ULL, id) >= p_drop2) ? keep2 : 0.f;
-  } else if (t >= 128 && t < 128 + NI * F1) {
-    const int u = t - 128, im = u / F1, j = u - im * F1;
-    const unsigned long long id = static_cast<unsigned long long>(n0 + im) * F1 + j;
-    S.m1[im][j] = (!training || hash_u01(seed ^ 0x27d4eb2fULL, id) >= p_drop1) ? keep1 : 0.f;
-  } else if (t >= 384 && t < 384 + NI) {
-    const int im = t - 384;
-    const bool ok = n0 + im < B;
-    S.valid[im] = ok ? 1.f : 0.f;
-    S.label[im] = ok ? static_cast<int>(tgt[n0 + im]) : 0;
-  }
+  static_assert(offsetof(CnnSmem, fc2b) == offsetof(CnnSmem, fc2w) + sizeof(float) * FC2N, "fc2w, fc2b adjacent");
+  u16x8 fr[2];  // conv2 forward fragments: stored to LDS at the end of P1
+  cnn_p0<true>(S, t, n0, B, images, tgt, params, frag, rng, p_drop2, p_drop1, training, fr);
   float* slab = slabs + static_cast<long>(blockIdx.x) * NSLABP + SLAB_OFS;
-  fr[0] = frag[t];  // conv2 forward fragments: stored to LDS at the end of P1
-  fr[1] = frag[min(t + T, NF2F - 1)];
   lds_sync();
   PDE_STAMP(1);
 
@@ -708,8 +760,11 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
     const float val = S.valid[im];
     const int y = S.label[im];  // (loaded in P0: a global load here would wait behind the w6 prefetch)
     const float ly = lanef(logit, __builtin_amdgcn_readfirstlane(4 * y));  // y: the wave's image label
-    const float inv_b = val / static_cast<float>(B);
-    const float dl = (__expf(logit - lse) - (v == y ? 1.f : 0.f)) * inv_b;  // d logit v (lanes of quad v)
+    // d logit v of the image's own loss (lanes of quad v), NOT yet divided by B: every gradient below is linear
+    // in it and passes through cnn_reduce_role, which applies 1 / B in fp32.  Scaled here, the bf16 operands
+    // (dH, d2, e1) rounded v / B, so an image's contribution depended on the batch it came in unless B was a
+    // power of two (for those, as the benchmark's, the scaling commutes with every rounding: same bits).
+    const float dl = (__expf(logit - lse) - (v == y ? 1.f : 0.f)) * val;
     if (lv && p == 0) S.dlog[im][v] = dl;
     if (lane == 0) S.lossim[im] = val * (lse - ly);
     // P5's dh = relu'(h1) * mask * (W2^T dlog) of THIS image, in the same wave: lane j < F1 gathers the 10
@@ -1222,7 +1277,7 @@ __global__ __launch_bounds__(256) void k_cnn_sgd(float* __restrict__ params, con
   write_frag(frag, p, w);
 }
 
-// grads (+)= gscale * (sum_wg slabs[wg] | dH^T . R2) in a fixed order (deterministic).
+// grads (+)= gscale / B * (sum_wg slabs[wg] | dH^T . R2) in a fixed order (deterministic).
 //  * slab blocks (blockIdx < RED_SLAB_BLOCKS): 8 waves over 16 float4 slab columns; lane = column + 16 x
 //    slab-lane, so one load instruction of a wave reads 4 slabs x 256 B and each thread keeps nwg/32
 //    independent float4 loads in flight;
@@ -1267,12 +1322,26 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
                                                 int* __restrict__ step, const XgmiView& xv, float xscale) {
   const int tid = threadIdx.x;
   const bool act = tid < RED_T;  // (k_cnn_train's threads past RED_T only join the barriers)
-  const float gs = gscale ? gscale[0] : 1.f;
   // world > 1 with a peer view: this block's gradients go through the one-shot xGMI exchange (stage to my
   // slot, flags, read all ranks' values in rank order, x xscale) before the store + SGD update
   const bool xchg = xv.size > 1;
-  // SGD operands requested up front: they do not depend on the reduction
-  const float lrate = hp ? hp[HP_LR] : 0.f, gsc = hp ? hp[HP_GRAD_SCALE] : 0.f;
+  // Each role requests its first batch of reduction operands (8 slab loads / 2 x CH activation loads) BEFORE
+  // the small operands: gscale[0], the hyper-parameters and the owner's params / grads do not depend on the
+  // reduction and are requested right behind that batch, as vector loads -- as scalar loads they were a wait
+  // for a memory round trip in front of the first slab request.
+  // k_cnn_train leaves its gradients unscaled (sums over the images, not means): 1 / B is applied here, in fp32,
+  // together with gscale
+  const float inv_b = 1.f / static_cast<float>(B);
+  float gs = 1.f, lrate = 0.f, gsc = 0.f;
+  auto load_scalars = [&]() {
+    int z = 0;  // a per-lane offset the compiler cannot prove uniform: global (vector) loads
+    asm("" : "+v"(z));
+    if (gscale) gs = gscale[z];
+    if (hp) {
+      lrate = hp[HP_LR + z];
+      gsc = hp[HP_GRAD_SCALE + z];
+    }
+  };
   const uint32_t epoch = xchg ? xgmi_epoch(xv, rb, s_epoch) : 0u;
   float* xmine = xchg ? xgmi_slot(xv, xv.rank, epoch) : nullptr;
   if (rb < RED_SLAB_BLOCKS) {
@@ -1291,19 +1360,34 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
 #pragma unroll
       for (int j = 0; j < 4; ++j) pj[j] = w2t ? O_W2 + (cg * 4 + j) * K2 + kidx : p4 * 4 + j;
     }
+    // the first batch of 8 slab loads: unconditional, from clamped rows / columns (a thread without a full
+    // batch adds zeros instead of the loaded values)
+    const bool live = act && c4 < NSLAB4;
+    const bool first = live && sl + 7 * RED_LANES < nwg;
+    f32x4 v8[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      v8[u] = s4[static_cast<long>(min(sl + u * RED_LANES, nwg - 1)) * (NSLABP / 4) + SLAB_OFS / 4 + min(c4, NSLAB4 - 1)];
+    load_scalars();
     f32x4 w0 = a0, g0 = a0;
-    if (owner && w2t) {
+    // (one shape for both column kinds, four dword loads: with a float4 load on a second path the two paths'
+    // results share registers, and the compiler drains the slab loads before it overwrites them)
+    if (owner) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (hp) w0[j] = params[pj[j]];
         if (accumulate) g0[j] = grads[pj[j]];
       }
-    } else {
-      if (owner && hp) w0 = reinterpret_cast<const f32x4*>(params)[p4];
-      if (owner && accumulate) g0 = reinterpret_cast<const f32x4*>(grads)[p4];
     }
-    if (act && c4 < NSLAB4) {
-      int b = sl;
+    {
+      const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+      a0 += first ? v8[0] + v8[4] : z4;
+      a1 += first ? v8[1] + v8[5] : z4;
+      a2 += first ? v8[2] + v8[6] : z4;
+      a3 += first ? v8[3] + v8[7] : z4;
+    }
+    if (live) {
+      int b = first ? sl + 8 * RED_LANES : sl;
       for (; b + 7 * RED_LANES < nwg; b += 8 * RED_LANES) {  // 8 independent loads in flight
         f32x4 v[8];
 #pragma unroll
@@ -1331,7 +1415,7 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
       v = part[col];
 #pragma unroll 8
       for (int k = 1; k < RED_LANES; ++k) v += part[k * RED_COLS + col];
-      v *= gs;
+      v *= gs * inv_b;
       if (xchg) reinterpret_cast<f32x4*>(xmine)[p4] = v;
     }
     bool ok = true;
@@ -1371,6 +1455,21 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
     const int kper = ((Bkp + 8 * 32 - 1) / (8 * 32)) * 32;  // this wave's K slice, a multiple of 32
     const int k0 = wid * kper, k1 = act ? min(Bkp, k0 + kper) : k0;
     const bool jv = j0 + lr < F1;
+    const uint16_t* arow = acts + static_cast<long>(jv ? j0 + lr : 0) * Bkp;
+    const uint16_t* brow = acts + static_cast<long>(F1 + i0 + lr) * Bkp;
+    constexpr int CH = 4;  // 32-deep chunks per pass: all 2 x CH loads in flight before the first MFMA
+    const u16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    // the first pass's 2 x CH operand loads: unconditional, from clamped columns (chunks past the wave's slice
+    // and rows past F1 multiply as zeros, as in the loop below)
+    u16x8 a1st[CH], b1st[CH];
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const int k = k0 + 32 * c + 8 * lg;
+      const int kc = k < k1 ? k : 0;
+      a1st[c] = *reinterpret_cast<const u16x8*>(arow + kc);
+      b1st[c] = *reinterpret_cast<const u16x8*>(brow + kc);
+    }
+    load_scalars();
     float w0[4] = {0.f, 0.f, 0.f, 0.f}, g0[4] = {0.f, 0.f, 0.f, 0.f};  // wave 0's outputs (j0 + 4 lg + r, i0 + lr)
     if (wid == 0 && act) {
 #pragma unroll
@@ -1383,12 +1482,20 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
         }
       }
     }
-    const uint16_t* arow = acts + static_cast<long>(jv ? j0 + lr : 0) * Bkp;
-    const uint16_t* brow = acts + static_cast<long>(F1 + i0 + lr) * Bkp;
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-    constexpr int CH = 4;  // 32-deep chunks per pass: all 2 x CH loads in flight before the first MFMA
-    const u16x8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int kb = k0; kb < k1; kb += 32 * CH) {
+    // (an empty slice runs the first pass on zeros: the accumulators stay +0, as if skipped)
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const bool ok = k0 + 32 * c + 8 * lg < k1;
+      a1st[c] = (ok && jv) ? a1st[c] : z8;
+      b1st[c] = ok ? b1st[c] : z8;
+    }
+#pragma unroll
+    for (int c = 0; c < CH; c += 2) {
+      acc0 = mfma(a1st[c], b1st[c], acc0);
+      acc1 = mfma(a1st[c + 1], b1st[c + 1], acc1);
+    }
+    for (int kb = k0 + 32 * CH; kb < k1; kb += 32 * CH) {
       u16x8 a[CH], b[CH];
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
@@ -1412,7 +1519,7 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
       v = wpart[lane];
 #pragma unroll
       for (int w = 1; w < RED_T / 64; ++w) v += wpart[w * 64 + lane];
-      v *= gs;
+      v *= gs * inv_b;
       if (xchg) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1480,6 +1587,9 @@ __global__ __launch_bounds__(RED_T) void k_cnn_reduce(const float* __restrict__ 
   __shared__ f32x4 part[RED_LANES * RED_COLS];  // slab: [lane][column]; fc1: [wave][lane] (same 8 KB)
   __shared__ uint32_t s_epoch;
   __shared__ int s_fail;
+  // every argument live here: the kernel-argument segment arrives behind one wait, ahead of the first request
+  asm volatile("" ::"s"(slabs), "s"(nwg), "s"(acts), "s"(gscale), "s"(grads), "s"(accumulate), "s"(loss_part), "s"(B),
+               "s"(loss), "s"(rng), "s"(params), "s"(hp), "s"(frag), "s"(step), "s"(xv.size), "s"(xscale), "s"(rb0));
   cnn_reduce_role(rb0 + blockIdx.x, part, &s_epoch, &s_fail, slabs, nwg, acts, gscale, grads, accumulate, loss_part, B,
                   loss, rng, params, hp, frag, step, xv, xscale);
 }
@@ -1562,42 +1672,13 @@ __global__ __launch_bounds__(T) void k_cnn_eval(const float* __restrict__ images
   const float* gFC1W = params + O_FC1W;
   const int n0 = blockIdx.x * NI;
 
-  // ---- P0: images -> bf16 (x, x1), conv1's fragment, the fp32 head weights; conv2's fragments are requested
-  // here and stored after conv1 (k_cnn_train's P0 without the backward's tables and the dropout masks).  Image
-  // addresses are clamped to the batch; an empty slot holds zeros.
-  const int qi = min(t, NI * NX / 4 - 1);
-  const int qim = (qi * 4) / NX, qoff = qi * 4 - qim * NX;
-  constexpr int NF2F = KS2 * 2 * 64, NF2D = KSD * 64;  // fragment image: [w2f | w2d | w1f]
+  // ---- P0 (cnn_p0): k_cnn_train's, without the backward's tables and the dropout masks; conv2's fragments
+  // (fr) are requested there and stored after conv1
+  asm volatile("" ::"s"(images), "s"(tgt), "s"(B), "s"(params), "s"(frag), "s"(logp), "s"(pred), "s"(stats),
+               "s"(loss_part));  // the kernel arguments behind one wait
+  constexpr int NF2F = KS2 * 2 * 64;
   u16x8 fr[2];
-  const u16x8 fw1 = frag[NF2F + NF2D + (t & 63)];
-  f32x4 img = *reinterpret_cast<const f32x4*>(images + static_cast<long>(min(n0 + qim, B - 1)) * NX + qoff);
-  if (t < NI * NX / 4) {
-    const int im = qim, off = qoff, n = n0 + im;
-    const f32x4 v = n < B ? img : f32x4{0.f, 0.f, 0.f, 0.f};
-    const int row = off / H0, col = off - row * H0;
-    uint16_t* dst = &S.x[im][row * XP + col];
-    const uint16_t b0 = f2bf(v[0]), b1 = f2bf(v[1]), b2 = f2bf(v[2]), b3 = f2bf(v[3]);
-    dst[0] = b0; dst[1] = b1; dst[2] = b2; dst[3] = b3;
-    uint16_t* d1 = &S.x1[im][row * XP + col];
-    if (col > 0) d1[-1] = b0;
-    d1[0] = b1; d1[1] = b2; d1[2] = b3;
-  }
-  for (int i = t; i < NI * H0 * (XP - H0 + 1); i += T) {  // zero columns: x 28.., x1 27..
-    const int r = i / (XP - H0 + 1), c = i - r * (XP - H0 + 1);
-    if (c > 0) (&S.x[0][0])[r * XP + H0 - 1 + c] = 0;
-    (&S.x1[0][0])[r * XP + H0 - 1 + c] = 0;
-  }
-  if (t < 64) S.w1f[t] = fw1;
-  for (int i = t; i < C1; i += T) S.b1[i] = params[O_B1 + i];
-  for (int i = t; i < C2; i += T) S.b2[i] = params[O_B2 + i];
-  for (int i = t; i < F1; i += T) S.fc1b[i] = params[O_FC1B + i];
-  for (int i = t; i < FC2N + F2; i += T) (&S.fc2w[0])[i] = params[O_FC2W + i];
-  if (t >= 384 && t < 384 + NI) {
-    const int im = t - 384;
-    S.label[im] = (tgt != nullptr && n0 + im < B) ? static_cast<int>(tgt[n0 + im]) : 0;
-  }
-  fr[0] = frag[t];
-  fr[1] = frag[min(t + T, NF2F - 1)];
+  cnn_p0<false>(S, t, n0, B, images, tgt, params, frag, nullptr, 0.f, 0.f, 0, fr);
   lds_sync();
 
   // ---- P1: conv1 + maxpool2 + relu on the accumulators (k_cnn_train's P1; only the channel-last r1n is kept)
