@@ -276,9 +276,8 @@ struct CnnSmem {
   unsigned char a2[NI][NIN];
 };
 static_assert(sizeof(CnnSmem) <= 160 * 1024, "LDS budget");
-static_assert((offsetof(CnnSmem, x1) - offsetof(CnnSmem, x)) / 4 % 32 == 9 &&
-                  (offsetof(CnnSmem, xone) - offsetof(CnnSmem, x)) / 4 % 32 == 4,
-              "x1 / xone bank offsets from x (P1 gathers, P9 B reads: scripts/p9_lds_model.py)");
+static_assert((offsetof(CnnSmem, xone) - offsetof(CnnSmem, x)) / 4 % 32 == 4,
+              "xone bank offset from x (P9 B reads: scripts/p9_lds_model.py; x1's: cnn_p1)");
 static_assert(offsetof(CnnSmem, w2f) == offsetof(CnnSmem, r1n) + sizeof(uint16_t) * NI * NC1 * C1P &&
                   sizeof(uint32_t) * NI * C1 * EP <= sizeof(uint16_t) * NI * NC1 * C1P + sizeof(u16x8) * KS2 * 2 * 64,
               "e1 aliases r1n + w2f");
@@ -288,6 +287,8 @@ static_assert(offsetof(CnnSmem, d2n) == offsetof(CnnSmem, w1f) + sizeof(u16x8) *
 static_assert(offsetof(CnnSmem, w2d) == offsetof(CnnSmem, w2f) + sizeof(u16x8) * KS2 * 2 * 64, "w2f, w2d adjacent");
 constexpr int NT2 = 16 / NW;  // conv2-wgrad N-tiles (250 -> 16 x 16) per wave
 constexpr int NFRAG = KS2 * 2 * 64 + KSD * 64 + 64;  // bf16 MFMA weight fragments (w2f, w2d, w1f)
+constexpr int NF2F = KS2 * 2 * 64, NF2D = KSD * 64;  // fragment image: [w2f | w2d | w1f]
+static_assert(NF2F <= 2 * T && NF2D <= 2 * T && NF2F + NF2D + 64 == NFRAG, "fragment slots");
 static_assert(offsetof(CnnSmem, w1f) == offsetof(CnnSmem, w2d) + sizeof(u16x8) * KSD * 64, "w2d, w1f adjacent");
 // fc1 forward: thread = (output j, 32-wide input chunk) over all images; fc1 backward dp2: thread = (input i,
 // chunk of fc1 outputs).  Their partial sums live in the w2f region (dead after P2), combined in a fixed
@@ -297,7 +298,6 @@ constexpr int DP2_JC = 3;               // fc1-output chunks for dp2 (16, 16, 18
 constexpr int DP2_J = 16;               // rows per chunk (the last one takes the rest)
 static_assert(F1 - DP2_J * (DP2_JC - 1) <= 20 && DP2_J % 4 == 0 && DHP >= DP2_J * (DP2_JC - 1) + 20, "dp2 chunks");
 static_assert(F1 * FC1_KC <= T && NIN * DP2_JC <= T, "fc1 work split");
-static_assert(sizeof(float) * NI * F1 * FC1_KC <= sizeof(u16x8) * KS2 * 2 * 64, "fc1 partials alias w2f");
 static_assert(sizeof(float) * NI * NIN * DP2_JC <= sizeof(u16x8) * KS2 * 2 * 64, "dp2 partials alias w2f");
 static_assert(NT2 * NW == 16, "conv2 wgrad tiling");
 
@@ -417,10 +417,9 @@ __device__ __forceinline__ void cnn_p0(Smem& S, int t, int n0, int B, const floa
                                        const u16x8* __restrict__ frag, const unsigned long long* __restrict__ rng,
                                        float p_drop2, float p_drop1, int training, u16x8 (&fr)[2]) {
   static_assert(NI * NX / 4 <= T, "one image quad per thread");
-  constexpr int NF2F = KS2 * 2 * 64, NF2D = KSD * 64;  // fragment image: [w2f | w2d | w1f]
-  static_assert(NF2F <= 2 * T && NF2F + NF2D + 64 == NFRAG, "fragment slots");
   constexpr int NH = C1 + C2 + F1 + FC2N + F2;  // 590 head parameters, one per thread
   static_assert(NH <= T && O_FC2W == O_FC1B + F1 && O_FC2B == O_FC2W + FC2N, "fc1b, fc2w, fc2b contiguous");
+  static_assert(offsetof(Smem, fc2b) == offsetof(Smem, fc2w) + sizeof(float) * FC2N, "fc2w, fc2b adjacent");
   static_assert((NI & (NI - 1)) == 0 && 384 % NI == 0, "label threads 384..: slot t & (NI - 1)");
   const int qi = min(t, NI * NX / 4 - 1);
   const int qim = (qi * 4) / NX, qoff = qi * 4 - qim * NX;
@@ -509,6 +508,210 @@ __device__ __forceinline__ void cnn_p0(Smem& S, int t, int n0, int B, const floa
   }
 }
 
+// ---- The forward P1-P4 of k_cnn_train (TRAIN) and k_cnn_eval: ONE set of functions, so the two kernels run
+// the same device code on the same operands in the same order -- their results agree bit for bit by
+// construction.  TRAIN adds what only the backward reads (r1, a1, a2, h1d) and the dropout masks.
+
+// max over a pooling window's 4 taps and the tap that holds it (the first tap wins a tie)
+__device__ __forceinline__ float pool4(const f32x4& v, int& am) {
+  am = 0;
+  float m = v[0];
+  if (v[1] > m) { m = v[1]; am = 1; }
+  if (v[2] > m) { m = v[2]; am = 2; }
+  if (v[3] > m) { m = v[3]; am = 3; }
+  return m;
+}
+
+// ---- P1: conv1 (MFMA, M = (cell, tap), K = (ky, kx6) 30 -> 32, N = co) + maxpool2 + relu ----------
+// K runs over 6-wide kernel rows (kx = 5 has zero weight): every k pair (kx even) is two consecutive
+// pixels, read as ONE aligned 4-byte LDS load -- from x when the window starts on an even column (dx = 0),
+// from the shifted copy x1 otherwise: 4 gathers per fragment instead of 8.
+template <bool TRAIN, class Smem>
+__device__ __forceinline__ void cnn_p1(Smem& S, int lane, int wid) {
+  static_assert((offsetof(Smem, x1) - offsetof(Smem, x)) / 4 % 32 == 9, "x1 bank offset from x (P1 gathers)");
+  const int lr = lane & 15, lg = lane >> 4;
+  int koff[4];  // pair p: k = 8 lg + 2p = (ky, kx) offset into the image; pairs past k = 30 read offset 0
+                // (finite pixels times w1f's zero rows: no mask)
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const int k = lg * 8 + 2 * p;
+    koff[p] = k < KS * 6 ? (k / 6) * XP + (k % 6) : 0;
+  }
+  const u16x8 bw = S.w1f[lane];
+  const int tap = lr & 3, dy = tap >> 1, dx = tap & 1;
+  const uint16_t* xsrc = dx ? &S.x1[0][0] - 1 : &S.x[0][0];  // x1[i - 1] = x[i]: odd starts become even
+  // a tile is 4 consecutive pooling cells of one cell row (12 % 4 == 0): image, cell row and first column
+  // are wave-uniform (scalar), the lane adds its cell (lr >> 2) and tap -- no per-lane division
+  static_assert(P1 % 4 == 0 && MT1 * 4 == NC1, "conv1 tiles: 4 cells of one row");
+  const uint16_t* xlane = xsrc + dy * XP + 2 * (lr >> 2) + dx;
+  auto gather = [&](int tile, u16x8& a) {
+    const int im = tile / MT1, t4 = tile - im * MT1, py = t4 / (P1 / 4), px0 = (t4 - py * (P1 / 4)) * 4;
+    const uint16_t* xb = xlane + im * NXP + 2 * py * XP + 2 * px0;
+    u32x4 v;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) v[p] = *reinterpret_cast<const uint32_t*>(xb + koff[p]);
+    a = __builtin_bit_cast(u16x8, v);
+  };
+  static_assert((NI * MT1) % NW == 0, "every wave runs the same number of conv1 tiles");
+  constexpr int NT1 = NI * MT1 / NW;  // 9 tiles per wave
+  // all of the wave's gathers first, then its MFMAs, then the epilogues: no tile waits on another's LDS
+  // round trip (a one-tile-ahead pipeline measured 3.0 us for this loop, r4p)
+  u16x8 ag[NT1];
+#pragma unroll
+  for (int u = 0; u < NT1; ++u) gather(wid + u * NW, ag[u]);
+  f32x4 accs[NT1];
+#pragma unroll
+  for (int u = 0; u < NT1; ++u) accs[u] = mfma(ag[u], bw, f32x4{0.f, 0.f, 0.f, 0.f});
+  const float bias1 = lr < C1 ? S.b1[lr] : 0.f;
+#pragma unroll
+  for (int u = 0; u < NT1; ++u) {
+    const int tile = wid + u * NW;
+    const int im = tile / MT1, c0 = (tile - im * MT1) * 4;
+    const int co = lr;  // rows (lg*4 + r) = taps r of cell c0 + lg
+    int am;
+    const float m = pool4(accs[u], am);
+    // lanes co >= C1: w1f's columns and bias1 are zero there, so r == 0 -- r1n's ci padding gets its zeros;
+    // their r1 / a1 stores are masked off (exec, no per-lane address selects)
+    const uint16_t r = f2bf(fmaxf(m + bias1, 0.f));
+    S.r1n[im][c0 + lg][co] = r;
+    if constexpr (TRAIN) {
+      if (r == 0) am = AM_DEAD;  // relu-dead: P7b's epilogue and P9 read the mask from a1
+      if (co < C1) {
+        S.r1[im][co * RP16 + c0 + lg] = r;
+        S.a1[im][co * RP8 + c0 + lg] = static_cast<unsigned char>(am);
+      }
+    }
+  }
+}
+
+// conv2 forward fragments (loaded in P0): bf16 MFMA order, straight 16-byte stores
+template <class Smem>
+__device__ __forceinline__ void cnn_store_w2f(Smem& S, int t, const u16x8 (&fr)[2]) {
+  u16x8* dst = &S.w2f[0][0][0];
+  dst[t] = fr[0];
+  if (t + T < NF2F) dst[t + T] = fr[1];
+}
+
+// fc1's weights for P3 (32 per thread, 8 x 16-B L2 loads) are requested before conv2: their latency hides under
+// it (registers: 78 -> ~110 VGPRs, no spill at 4 waves per SIMD)
+__device__ __forceinline__ void cnn_fc1_rows(int t, const float* __restrict__ gFC1W, f32x4 (&w3)[8]) {
+  if (t < F1 * FC1_KC) {
+    const int j = t / FC1_KC, kc = t - j * FC1_KC;
+    const f32x4* w4 = reinterpret_cast<const f32x4*>(gFC1W + j * NIN + kc * 4);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) w3[q] = w4[q * (FC1_KC)];
+  }
+}
+
+// ---- P2: conv2 (MFMA, M = (cell, tap) 64/image = 4 M-tiles, K = (ci,ky,kx) 250 -> 256, N = co 20 -> 32)
+//          + dropout2d + maxpool2 + relu.  One (image, M-tile) per wave iteration, both N-tiles.
+template <bool TRAIN, class Smem>
+__device__ __forceinline__ void cnn_p2(Smem& S, int lane, int wid) {
+  const int lr = lane & 15, lg = lane >> 4;
+  for (int mtile = wid; mtile < NI * 4; mtile += NW) {
+    const int im = mtile >> 2, mt = mtile & 3;
+    const int tap = lr & 3, dy = tap >> 1, dx = tap & 1;
+    const int cell = mt * 4 + (lr >> 2), py = cell >> 2, px = cell & 3;
+    const int rb = (2 * py + dy) * P1 + 2 * px + dx;
+    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+    const uint16_t* r1n = &S.r1n[im][0][(lg & 1) * 8];
+#pragma unroll
+    for (int ks = 0; ks < KS2; ++ks) {
+      const int tp = 2 * ks + (lg >> 1), ky = tp / KS, kx = tp - ky * KS;
+      const u16x8 a = tp < KS * KS ? *reinterpret_cast<const u16x8*>(r1n + (rb + ky * P1 + kx) * C1P)
+                                   : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      acc0 = mfma(a, S.w2f[ks][0][lane], acc0);
+      acc1 = mfma(a, S.w2f[ks][1][lane], acc1);
+    }
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+      const int co = nt * 16 + lr;
+      if (co < C2) {
+        int am;
+        const float m = pool4(nt == 0 ? acc0 : acc1, am);
+        const int q = co * NC2 + mt * 4 + lg;
+        if constexpr (TRAIN) {
+          S.r2[im][q] = fmaxf((m + S.b2[co]) * S.mc2[im][co], 0.f);
+          S.a2[im][q] = static_cast<unsigned char>(am);
+        } else {
+          S.r2[im][q] = fmaxf(m + S.b2[co], 0.f);
+        }
+      }
+    }
+  }
+}
+
+// ---- P3: fc1 + relu + dropout.  Thread (j, kc): 32 weights of row j (8 x 16-B L2 loads, all in flight
+// together) against the 4 images' inputs; partials [kc][im][j] summed in kc order. -------------------
+template <bool TRAIN, class Smem>
+__device__ __forceinline__ void cnn_p3(Smem& S, int t, const f32x4 (&w3)[8]) {
+  static_assert(sizeof(float) * NI * F1 * FC1_KC <= sizeof(Smem::w2f), "fc1 partials alias w2f");
+  float* part = reinterpret_cast<float*>(&S.w2f[0][0][0]);
+  if (t < F1 * FC1_KC) {
+    const int j = t / FC1_KC, kc = t - j * FC1_KC;
+    // chunk kc = inputs {40 q + 4 kc .. +3 : q = 0..7}: the 10 chunks of a wave read 10 consecutive
+    // float4s of r2 (conflict-free), and adjacent lanes load adjacent 16 B of the weight row (w3, loaded
+    // before P2)
+    const f32x4* w = w3;
+    float s4[NI] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+#pragma unroll
+      for (int im = 0; im < NI; ++im) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(&S.r2[im][q * 4 * FC1_KC + kc * 4]);
+        s4[im] += w[q][0] * x[0] + w[q][1] * x[1] + w[q][2] * x[2] + w[q][3] * x[3];
+      }
+#pragma unroll
+    for (int im = 0; im < NI; ++im) part[(kc * NI + im) * F1 + j] = s4[im];
+  }
+  lds_sync();
+  if (t < NI * F1) {
+    const int im = t / F1, j = t - im * F1;
+    float s1 = S.fc1b[j];
+#pragma unroll
+    for (int kc = 0; kc < FC1_KC; ++kc) s1 += part[(kc * NI + im) * F1 + j];
+    const float h = fmaxf(s1, 0.f);
+    S.h1[im][j] = h;
+    if constexpr (TRAIN) S.h1d[im][j] = h * S.m1[im][j];
+  }
+}
+
+// ---- P4's head: fc2 logits and log_softmax of ONE image by ONE wave, no block barrier in between.
+// Lane l < 4 F2 computes a quarter of logit v = l / 4 (rows j = l % 4 + 4 k), the quad sums it; the softmax
+// reductions run across the wave's lanes (one thread per image summing serially took ~1.5 us).
+// `h`: the fc1 output row of image slot `im` (h1d in training, h1 in evaluation).
+struct CnnHead {
+  float logit;  // lanes of quad v: logit v
+  float lse;    // log-sum-exp of the 10 logits
+  float ly;     // the label's logit
+  int y;        // the label
+};
+template <class Smem>
+__device__ __forceinline__ CnnHead cnn_head(const Smem& S, const float* h, int im, int lane) {
+  static_assert(4 * F2 <= 64, "P4: a lane quad per logit");
+  const int v = lane >> 2, p = lane & 3;
+  const bool lv = v < F2;
+  const int vr = lv ? v : 0;
+  float s = 0.f;
+  // (fully unrolled, like every loop between the w6 prefetch and P6: a loop header makes the compiler wait
+  // for ALL outstanding global loads, w6 included)
+#pragma unroll
+  for (int k = 0; k < (F1 + 3) / 4; ++k) {
+    const int j = p + 4 * k;
+    if (j < F1) s += S.fc2w[vr * F1 + j] * h[j];
+  }
+  s += dppf<DPP_XOR1>(s);
+  s += dppf<DPP_XOR2>(s);
+  const float logit = s + S.fc2b[vr];
+  const float m = wave_max_dpp(lv ? logit : -INFINITY);
+  const float ex = __expf(logit - m);
+  const float se = wave_sum_dpp(lv && p == 0 ? ex : 0.f);
+  const float lse = m + __logf(se);
+  const int y = S.label[im];  // (loaded in P0: a global load here would wait behind the w6 prefetch)
+  const float ly = lanef(logit, __builtin_amdgcn_readfirstlane(4 * y));  // y: the wave's image label
+  return {logit, lse, ly, y};
+}
+
 // BREG: P7b's B operand (the conv2 data-gradient fragments, identical for every wave) is loaded from the
 // fragment image into registers at the start of P7a instead of being staged in LDS -- a quarter of P7b's LDS
 // traffic moves to the vector-memory path (L1 / L2 hits), which runs beside the LDS.
@@ -551,167 +754,31 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
   // end of P1, its data-gradient fragments (w2d) are requested in P4 and stored at the end of P6 -- their
   // latency is on no phase's critical path, and the burst of fragment reads every workgroup makes at the
   // start is 28 KB instead of 47 KB.
-  constexpr int NF2F = KS2 * 2 * 64, NF2D = KSD * 64;  // fragment image: [w2f | w2d | w1f]
-  static_assert(NF2F <= 2 * T && NF2D <= 2 * T && NF2F + NF2D + 64 == NFRAG, "fragment slots");
-  static_assert(offsetof(CnnSmem, fc2b) == offsetof(CnnSmem, fc2w) + sizeof(float) * FC2N, "fc2w, fc2b adjacent");
   u16x8 fr[2];  // conv2 forward fragments: stored to LDS at the end of P1
   cnn_p0<true>(S, t, n0, B, images, tgt, params, frag, rng, p_drop2, p_drop1, training, fr);
   float* slab = slabs + static_cast<long>(blockIdx.x) * NSLABP + SLAB_OFS;
   lds_sync();
   PDE_STAMP(1);
 
-  // ---- P1: conv1 (MFMA, M = (cell, tap), K = (ky, kx6) 30 -> 32, N = co) + maxpool2 + relu ----------
-  // K runs over 6-wide kernel rows (kx = 5 has zero weight): every k pair (kx even) is two consecutive
-  // pixels, read as ONE aligned 4-byte LDS load -- from x when the window starts on an even column (dx = 0),
-  // from the shifted copy x1 otherwise: 4 gathers per fragment instead of 8.
-  {
-    int koff[4];  // pair p: k = 8 lg + 2p = (ky, kx) offset into the image; pairs past k = 30 read offset 0
-                  // (finite pixels times w1f's zero rows: no mask)
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int k = lg * 8 + 2 * p;
-      koff[p] = k < KS * 6 ? (k / 6) * XP + (k % 6) : 0;
-    }
-    const u16x8 bw = S.w1f[lane];
-    const int tap = lr & 3, dy = tap >> 1, dx = tap & 1;
-    const uint16_t* xsrc = dx ? &S.x1[0][0] - 1 : &S.x[0][0];  // x1[i - 1] = x[i]: odd starts become even
-    // a tile is 4 consecutive pooling cells of one cell row (12 % 4 == 0): image, cell row and first column
-    // are wave-uniform (scalar), the lane adds its cell (lr >> 2) and tap -- no per-lane division
-    static_assert(P1 % 4 == 0 && MT1 * 4 == NC1, "conv1 tiles: 4 cells of one row");
-    const uint16_t* xlane = xsrc + dy * XP + 2 * (lr >> 2) + dx;
-    auto gather = [&](int tile, u16x8& a) {
-      const int im = tile / MT1, t4 = tile - im * MT1, py = t4 / (P1 / 4), px0 = (t4 - py * (P1 / 4)) * 4;
-      const uint16_t* xb = xlane + im * NXP + 2 * py * XP + 2 * px0;
-      u32x4 v;
-#pragma unroll
-      for (int p = 0; p < 4; ++p) v[p] = *reinterpret_cast<const uint32_t*>(xb + koff[p]);
-      a = __builtin_bit_cast(u16x8, v);
-    };
-    static_assert((NI * MT1) % NW == 0, "every wave runs the same number of conv1 tiles");
-    constexpr int NT1 = NI * MT1 / NW;  // 9 tiles per wave
-    // all of the wave's gathers first, then its MFMAs, then the epilogues: no tile waits on another's LDS
-    // round trip (a one-tile-ahead pipeline measured 3.0 us for this loop, r4p)
-    u16x8 ag[NT1];
-#pragma unroll
-    for (int u = 0; u < NT1; ++u) gather(wid + u * NW, ag[u]);
-    f32x4 accs[NT1];
-#pragma unroll
-    for (int u = 0; u < NT1; ++u) accs[u] = mfma(ag[u], bw, f32x4{0.f, 0.f, 0.f, 0.f});
-    const float bias1 = lr < C1 ? S.b1[lr] : 0.f;
-#pragma unroll
-    for (int u = 0; u < NT1; ++u) {
-      const int tile = wid + u * NW;
-      const int im = tile / MT1, c0 = (tile - im * MT1) * 4;
-      const f32x4 acc = accs[u];
-      const int co = lr;  // rows (lg*4 + r) = taps r of cell c0 + lg
-      // lanes co >= C1: w1f's columns and bias1 are zero there, so r == 0 -- r1n's ci padding gets its zeros;
-      // their r1 / a1 stores are masked off (exec, no per-lane address selects)
-      const bool live = co < C1;
-      int am = 0;
-      float m = acc[0];
-      if (acc[1] > m) { m = acc[1]; am = 1; }
-      if (acc[2] > m) { m = acc[2]; am = 2; }
-      if (acc[3] > m) { m = acc[3]; am = 3; }
-      const uint16_t r = f2bf(fmaxf(m + bias1, 0.f));
-      if (r == 0) am = AM_DEAD;  // relu-dead: P7b's epilogue and P9 read the mask from a1
-      S.r1n[im][c0 + lg][co] = r;
-      if (live) {
-        S.r1[im][co * RP16 + c0 + lg] = r;
-        S.a1[im][co * RP8 + c0 + lg] = static_cast<unsigned char>(am);
-      }
-    }
-  }
+  // ---- P1 .. P4's head: the forward shared with k_cnn_eval (cnn_p1 .. cnn_head above); the barriers and the
+  // stamps between the phases stay here.  P1: conv1 + maxpool2 + relu
+  cnn_p1<true>(S, lane, wid);
   if (stamps != nullptr) {  // diagnostic: conv1 done (waves 0 / 7 / 15), before the fragment stores
     if (t == 0) stamps[blockIdx.x * 16 + 13] = wall_clock64();
     if (t == 15 * 64) stamps[blockIdx.x * 16 + 15] = wall_clock64();
   }
-  if (!(xmap & 2)) {  // conv2 forward fragments (loaded in P0): bf16 MFMA order, straight 16-byte stores
-    // (xmap & 2: timing diagnostic, the stores and their wait skipped -- results invalid)
-    u16x8* dst = &S.w2f[0][0][0];
-    dst[t] = fr[0];
-    if (t + T < NF2F) dst[t + T] = fr[1];
-  }
+  // (xmap & 2: timing diagnostic, the stores and their wait skipped -- results invalid)
+  if (!(xmap & 2)) cnn_store_w2f(S, t, fr);
   lds_sync();
   PDE_STAMP(2);
 
-  // fc1's weights for P3 (32 per thread, 8 x 16-B L2 loads) are requested now: their latency hides under
-  // conv2 (registers: 78 -> ~110 VGPRs, no spill at 4 waves per SIMD)
-  f32x4 w3[8];
-  if (t < F1 * FC1_KC) {
-    const int j = t / FC1_KC, kc = t - j * FC1_KC;
-    const f32x4* w4 = reinterpret_cast<const f32x4*>(gFC1W + j * NIN + kc * 4);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) w3[q] = w4[q * (FC1_KC)];
-  }
-
-  // ---- P2: conv2 (MFMA, M = (cell, tap) 64/image = 4 M-tiles, K = (ci,ky,kx) 250 -> 256, N = co 20 -> 32)
-  //          + dropout2d + maxpool2 + relu.  One (image, M-tile) per wave iteration, both N-tiles.
-  for (int mtile = wid; mtile < NI * 4; mtile += NW) {
-    const int im = mtile >> 2, mt = mtile & 3;
-    const int tap = lr & 3, dy = tap >> 1, dx = tap & 1;
-    const int cell = mt * 4 + (lr >> 2), py = cell >> 2, px = cell & 3;
-    const int rb = (2 * py + dy) * P1 + 2 * px + dx;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-    const uint16_t* r1n = &S.r1n[im][0][(lg & 1) * 8];
-#pragma unroll
-    for (int ks = 0; ks < KS2; ++ks) {
-      const int tp = 2 * ks + (lg >> 1), ky = tp / KS, kx = tp - ky * KS;
-      const u16x8 a = tp < KS * KS ? *reinterpret_cast<const u16x8*>(r1n + (rb + ky * P1 + kx) * C1P)
-                                   : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      acc0 = mfma(a, S.w2f[ks][0][lane], acc0);
-      acc1 = mfma(a, S.w2f[ks][1][lane], acc1);
-    }
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      const int co = nt * 16 + lr;
-      if (co < C2) {
-        const f32x4 v = nt == 0 ? acc0 : acc1;
-        int am = 0;
-        float m = v[0];
-        if (v[1] > m) { m = v[1]; am = 1; }
-        if (v[2] > m) { m = v[2]; am = 2; }
-        if (v[3] > m) { m = v[3]; am = 3; }
-        const int q = co * NC2 + mt * 4 + lg;
-        S.r2[im][q] = fmaxf((m + S.b2[co]) * S.mc2[im][co], 0.f);
-        S.a2[im][q] = static_cast<unsigned char>(am);
-      }
-    }
-  }
+  f32x4 w3[8];  // fc1's rows for P3, requested ahead of P2: conv2 + dropout2d + maxpool2 + relu
+  cnn_fc1_rows(t, gFC1W, w3);
+  cnn_p2<true>(S, lane, wid);
   lds_sync();
   PDE_STAMP(3);
 
-  // ---- P3: fc1 + relu + dropout.  Thread (j, kc): 32 weights of row j (8 x 16-B L2 loads, all in flight
-  // together) against the 4 images' inputs; partials [kc][im][j] summed in kc order. -------------------
-  {
-    float* part = reinterpret_cast<float*>(&S.w2f[0][0][0]);
-    if (t < F1 * FC1_KC) {
-      const int j = t / FC1_KC, kc = t - j * FC1_KC;
-      // chunk kc = inputs {40 q + 4 kc .. +3 : q = 0..7}: the 10 chunks of a wave read 10 consecutive
-      // float4s of r2 (conflict-free), and adjacent lanes load adjacent 16 B of the weight row (w3, loaded
-      // before P2)
-      const f32x4* w = w3;
-      float s4[NI] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-#pragma unroll
-        for (int im = 0; im < NI; ++im) {
-          const f32x4 x = *reinterpret_cast<const f32x4*>(&S.r2[im][q * 4 * FC1_KC + kc * 4]);
-          s4[im] += w[q][0] * x[0] + w[q][1] * x[1] + w[q][2] * x[2] + w[q][3] * x[3];
-        }
-#pragma unroll
-      for (int im = 0; im < NI; ++im) part[(kc * NI + im) * F1 + j] = s4[im];
-    }
-    lds_sync();
-    if (t < NI * F1) {
-      const int im = t / F1, j = t - im * F1;
-      float s1 = S.fc1b[j];
-#pragma unroll
-      for (int kc = 0; kc < FC1_KC; ++kc) s1 += part[(kc * NI + im) * F1 + j];
-      const float h = fmaxf(s1, 0.f);
-      S.h1[im][j] = h;
-      S.h1d[im][j] = h * S.m1[im][j];
-    }
-  }
+  cnn_p3<true>(S, t, w3);  // P3: fc1 + relu + dropout
   lds_sync();
   PDE_STAMP(4);
 
@@ -734,32 +801,13 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
     fd[1] = frag[NF2F + min(t + T, NF2D - 1)];
   }
 
-  // ---- P4: fc2 logits, then log_softmax + NLL + dlogits: ONE WAVE PER IMAGE, no block barrier in between.
-  // Lane l < 4 F2 computes a quarter of logit v = l / 4 (rows j = l % 4 + 4 k), the quad sums it; the softmax
-  // reductions run across the wave's lanes (one thread per image summing serially took ~1.5 us).
-  static_assert(NI <= NW && 4 * F2 <= 64, "P4: a wave per image, a lane quad per logit");
+  // ---- P4: fc2 logits, then log_softmax (cnn_head) + NLL + dlogits: ONE WAVE PER IMAGE.
+  static_assert(NI <= NW, "P4: a wave per image");
   if (wid < NI) {
     const int im = wid, v = lane >> 2, p = lane & 3;
     const bool lv = v < F2;
-    const int vr = lv ? v : 0;
-    float s = 0.f;
-    // (fully unrolled, like every loop between the w6 prefetch and P6: a loop header makes the compiler wait
-    // for ALL outstanding global loads, w6 included)
-#pragma unroll
-    for (int k = 0; k < (F1 + 3) / 4; ++k) {
-      const int j = p + 4 * k;
-      if (j < F1) s += S.fc2w[vr * F1 + j] * S.h1d[im][j];
-    }
-    s += dppf<DPP_XOR1>(s);
-    s += dppf<DPP_XOR2>(s);
-    const float logit = s + S.fc2b[vr];
-    const float m = wave_max_dpp(lv ? logit : -INFINITY);
-    const float ex = __expf(logit - m);
-    const float se = wave_sum_dpp(lv && p == 0 ? ex : 0.f);
-    const float lse = m + __logf(se);
+    const auto [logit, lse, ly, y] = cnn_head(S, S.h1d[im], im, lane);
     const float val = S.valid[im];
-    const int y = S.label[im];  // (loaded in P0: a global load here would wait behind the w6 prefetch)
-    const float ly = lanef(logit, __builtin_amdgcn_readfirstlane(4 * y));  // y: the wave's image label
     // d logit v of the image's own loss (lanes of quad v), NOT yet divided by B: every gradient below is linear
     // in it and passes through cnn_reduce_role, which applies 1 / B in fp32.  Scaled here, the bf16 operands
     // (dH, d2, e1) rounded v / B, so an image's contribution depended on the batch it came in unless B was a
@@ -1604,9 +1652,10 @@ __device__ void cnn_fused_tail(const CnnTail& tl, int rb, f32x4* part, uint32_t*
 }
 
 // ---------------------------------------------------------------------------------------------
-// Forward-only evaluation: k_cnn_train's P0-P4 in eval mode (no dropout), nothing else.  Same operands, same
-// precision and the same accumulation order in every stage, so a batch's summed NLL equals the training
-// kernel's eval-mode loss x B; the outputs are the log-probabilities, their argmax and running totals.
+// Forward-only evaluation: k_cnn_train's P0-P4 in eval mode (no dropout), nothing else.  The forward IS the
+// training kernel's code, not a copy of it: cnn_p0 .. cnn_head instantiated without TRAIN, over the smaller LDS
+// image below -- so a batch's summed NLL equals the training kernel's eval-mode loss x B; the outputs are the
+// log-probabilities, their argmax and running totals.
 //
 // Geometry: NI = 4 images per 16-wave workgroup, as in training.  The forward is the same chain of short
 // dependent phases, so it is latency-bound in the same way and 4 waves per image hide it; at the entry scripts'
@@ -1616,15 +1665,6 @@ __device__ void cnn_fused_tail(const CnnTail& tl, int rb, f32x4* part, uint32_t*
 // 16-wave workgroup needs 8 waves per SIMD, i.e. <= 64 VGPRs, and the kernel takes 72 (forcing 64 spills 8
 // registers to scratch) -- so larger batches run one workgroup per CU, in rounds.
 // ---------------------------------------------------------------------------------------------
-// max over a pooling window's 4 taps, by k_cnn_train's compare chain (the first tap wins a tie)
-__device__ __forceinline__ float pool4(const f32x4& v) {
-  float m = v[0];
-  if (v[1] > m) m = v[1];
-  if (v[2] > m) m = v[2];
-  if (v[3] > m) m = v[3];
-  return m;
-}
-
 struct CnnEvalSmem {
   alignas(16) uint16_t r1n[NI][NC1][C1P];  // relu(maxpool(conv1)) channel-last (CnnSmem::r1n)
   alignas(16) u16x8 w2f[KS2][2][64];       // conv2 B fragments; fc1's partials later (dead after conv2)
@@ -1643,10 +1683,8 @@ struct CnnEvalSmem {
   int hit[NI];                             // pred == y per image (0 for an empty slot)
   int label[NI];
 };
-static_assert((offsetof(CnnEvalSmem, x1) - offsetof(CnnEvalSmem, x)) / 4 % 32 == 9,
-              "x1 bank offset from x (P1 gathers)");
-static_assert(offsetof(CnnEvalSmem, fc2b) == offsetof(CnnEvalSmem, fc2w) + sizeof(float) * FC2N, "fc2w, fc2b adjacent");
-static_assert(sizeof(float) * NI * F1 * FC1_KC <= sizeof(u16x8) * KS2 * 2 * 64, "fc1 partials alias w2f");
+// (the layout conditions of the forward -- x1's bank offset, fc2w / fc2b adjacent, fc1's partials inside w2f --
+// are asserted by cnn_p0 / cnn_p1 / cnn_p3 for every struct they are instantiated with)
 static_assert(sizeof(CnnEvalSmem) <= 80 * 1024, "LDS budget");
 
 // The running totals of CnnEvalStats (models/cnn_fused.py): four 8-byte words.
@@ -1668,149 +1706,33 @@ __global__ __launch_bounds__(T) void k_cnn_eval(const float* __restrict__ images
   const int t = threadIdx.x;
   const int lane = t & 63;
   const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int lr = lane & 15, lg = lane >> 4;
-  const float* gFC1W = params + O_FC1W;
   const int n0 = blockIdx.x * NI;
 
-  // ---- P0 (cnn_p0): k_cnn_train's, without the backward's tables and the dropout masks; conv2's fragments
-  // (fr) are requested there and stored after conv1
+  // ---- P0 (cnn_p0) without the backward's tables and the dropout masks; conv2's fragments (fr) are requested
+  // there and stored after conv1
   asm volatile("" ::"s"(images), "s"(tgt), "s"(B), "s"(params), "s"(frag), "s"(logp), "s"(pred), "s"(stats),
                "s"(loss_part));  // the kernel arguments behind one wait
-  constexpr int NF2F = KS2 * 2 * 64;
   u16x8 fr[2];
   cnn_p0<false>(S, t, n0, B, images, tgt, params, frag, nullptr, 0.f, 0.f, 0, fr);
   lds_sync();
 
-  // ---- P1: conv1 + maxpool2 + relu on the accumulators (k_cnn_train's P1; only the channel-last r1n is kept)
-  {
-    int koff[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int k = lg * 8 + 2 * p;
-      koff[p] = k < KS * 6 ? (k / 6) * XP + (k % 6) : 0;
-    }
-    const u16x8 bw = S.w1f[lane];
-    const int tap = lr & 3, dy = tap >> 1, dx = tap & 1;
-    const uint16_t* xsrc = dx ? &S.x1[0][0] - 1 : &S.x[0][0];
-    const uint16_t* xlane = xsrc + dy * XP + 2 * (lr >> 2) + dx;
-    auto gather = [&](int tile, u16x8& a) {
-      const int im = tile / MT1, t4 = tile - im * MT1, py = t4 / (P1 / 4), px0 = (t4 - py * (P1 / 4)) * 4;
-      const uint16_t* xb = xlane + im * NXP + 2 * py * XP + 2 * px0;
-      u32x4 v;
-#pragma unroll
-      for (int p = 0; p < 4; ++p) v[p] = *reinterpret_cast<const uint32_t*>(xb + koff[p]);
-      a = __builtin_bit_cast(u16x8, v);
-    };
-    constexpr int NT1 = NI * MT1 / NW;  // 9 tiles per wave
-    u16x8 ag[NT1];
-#pragma unroll
-    for (int u = 0; u < NT1; ++u) gather(wid + u * NW, ag[u]);
-    f32x4 accs[NT1];
-#pragma unroll
-    for (int u = 0; u < NT1; ++u) accs[u] = mfma(ag[u], bw, f32x4{0.f, 0.f, 0.f, 0.f});
-    const float bias1 = lr < C1 ? S.b1[lr] : 0.f;
-#pragma unroll
-    for (int u = 0; u < NT1; ++u) {
-      const int tile = wid + u * NW;
-      const int im = tile / MT1, c0 = (tile - im * MT1) * 4;
-      const f32x4 acc = accs[u];
-      const float m = pool4(acc);
-      // lanes co >= C1: w1f's columns and bias1 are zero there, so r1n's ci padding gets its zeros
-      S.r1n[im][c0 + lg][lr] = f2bf(fmaxf(m + bias1, 0.f));
-    }
-  }
-  {
-    u16x8* dst = &S.w2f[0][0][0];
-    dst[t] = fr[0];
-    if (t + T < NF2F) dst[t + T] = fr[1];
-  }
+  // ---- P1-P3: conv1 (only the channel-last r1n is kept), conv2, fc1, each + its pooling / relu, no dropout
+  cnn_p1<false>(S, lane, wid);
+  cnn_store_w2f(S, t, fr);
   lds_sync();
-
-  // fc1's weights for P3, requested now: their L2 latency hides under conv2
   f32x4 w3[8];
-  if (t < F1 * FC1_KC) {
-    const int j = t / FC1_KC, kc = t - j * FC1_KC;
-    const f32x4* w4 = reinterpret_cast<const f32x4*>(gFC1W + j * NIN + kc * 4);
-#pragma unroll
-    for (int q = 0; q < 8; ++q) w3[q] = w4[q * (FC1_KC)];
-  }
-
-  // ---- P2: conv2 (k-steps ascending) + bias + maxpool2 + relu on the accumulators (k_cnn_train's P2)
-  for (int mtile = wid; mtile < NI * 4; mtile += NW) {
-    const int im = mtile >> 2, mt = mtile & 3;
-    const int tap = lr & 3, dy = tap >> 1, dx = tap & 1;
-    const int cell = mt * 4 + (lr >> 2), py = cell >> 2, px = cell & 3;
-    const int rb = (2 * py + dy) * P1 + 2 * px + dx;
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
-    const uint16_t* r1n = &S.r1n[im][0][(lg & 1) * 8];
-#pragma unroll
-    for (int ks = 0; ks < KS2; ++ks) {
-      const int tp = 2 * ks + (lg >> 1), ky = tp / KS, kx = tp - ky * KS;
-      const u16x8 a = tp < KS * KS ? *reinterpret_cast<const u16x8*>(r1n + (rb + ky * P1 + kx) * C1P)
-                                   : u16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      acc0 = mfma(a, S.w2f[ks][0][lane], acc0);
-      acc1 = mfma(a, S.w2f[ks][1][lane], acc1);
-    }
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      const int co = nt * 16 + lr;
-      if (co < C2) {
-        const f32x4 v = nt == 0 ? acc0 : acc1;
-        const float m = pool4(v);
-        S.r2[im][co * NC2 + mt * 4 + lg] = fmaxf(m + S.b2[co], 0.f);
-      }
-    }
-  }
+  cnn_fc1_rows(t, params + O_FC1W, w3);
+  cnn_p2<false>(S, lane, wid);
+  lds_sync();
+  cnn_p3<false>(S, t, w3);
   lds_sync();
 
-  // ---- P3: fc1 + relu (k_cnn_train's P3: partials [kc][im][j] summed in kc order)
-  {
-    float* part = reinterpret_cast<float*>(&S.w2f[0][0][0]);
-    if (t < F1 * FC1_KC) {
-      const int j = t / FC1_KC, kc = t - j * FC1_KC;
-      float s4[NI] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int q = 0; q < 8; ++q)
-#pragma unroll
-        for (int im = 0; im < NI; ++im) {
-          const f32x4 x = *reinterpret_cast<const f32x4*>(&S.r2[im][q * 4 * FC1_KC + kc * 4]);
-          s4[im] += w3[q][0] * x[0] + w3[q][1] * x[1] + w3[q][2] * x[2] + w3[q][3] * x[3];
-        }
-#pragma unroll
-      for (int im = 0; im < NI; ++im) part[(kc * NI + im) * F1 + j] = s4[im];
-    }
-    lds_sync();
-    if (t < NI * F1) {
-      const int im = t / F1, j = t - im * F1;
-      float s1 = S.fc1b[j];
-#pragma unroll
-      for (int kc = 0; kc < FC1_KC; ++kc) s1 += part[(kc * NI + im) * F1 + j];
-      S.h1[im][j] = fmaxf(s1, 0.f);
-    }
-  }
-  lds_sync();
-
-  // ---- P4: fc2 + log_softmax, one wave per image (k_cnn_train's P4), then the outputs: the 10
+  // ---- P4: fc2 + log_softmax, one wave per image (cnn_head), then the outputs: the 10
   // log-probabilities, their argmax (lowest index on a tie) and the image's NLL / hit for the totals
   if (wid < NI) {
     const int im = wid, v = lane >> 2, p = lane & 3;
     const bool lv = v < F2;
-    const int vr = lv ? v : 0;
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < (F1 + 3) / 4; ++k) {
-      const int j = p + 4 * k;
-      if (j < F1) s += S.fc2w[vr * F1 + j] * S.h1[im][j];
-    }
-    s += dppf<DPP_XOR1>(s);
-    s += dppf<DPP_XOR2>(s);
-    const float logit = s + S.fc2b[vr];
-    const float m = wave_max_dpp(lv ? logit : -INFINITY);
-    const float ex = __expf(logit - m);
-    const float se = wave_sum_dpp(lv && p == 0 ? ex : 0.f);
-    const float lse = m + __logf(se);
-    const int y = S.label[im];
-    const float ly = lanef(logit, __builtin_amdgcn_readfirstlane(4 * y));
+    const auto [logit, lse, ly, y] = cnn_head(S, S.h1[im], im, lane);
     const float lp = logit - lse;
     const float best = wave_max_dpp(lv ? lp : -INFINITY);
     const float cand = (lv && lp == best) ? static_cast<float>(v) : static_cast<float>(F2);
