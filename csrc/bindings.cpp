@@ -388,6 +388,45 @@ void gather_rows_counter(const Tensor& src, const Tensor& labels, const Tensor& 
         "gather_rows_counter");
 }
 
+// uint8 gather + normalise (pde::gather_rows_u8): x_out [rows, R] fp32 = table[src_u8[idx[...]]], y_out [rows]
+// int64 = labels[idx[...]], rows = y_out.numel().  counter undefined: list positions start .. start + rows - 1;
+// else the device counter's slice (and the counter advances).  Positions past the list repeat its last entry.
+void gather_rows_u8_impl(const char* what, const Tensor& src, const Tensor& labels, const Tensor& idx,
+                         const Tensor& table, const Tensor* counter, Tensor& x_out, Tensor& y_out, int64_t start) {
+  CHECK_IN(src); CHECK_IN(labels); CHECK_IN(idx); CHECK_IN(table); CHECK_IN(x_out); CHECK_F32(x_out); CHECK_IN(y_out);
+  TORCH_CHECK(src.scalar_type() == at::kByte && src.dim() == 2, what, ": src must be a 2-D uint8 tensor");
+  TORCH_CHECK(labels.scalar_type() == at::kLong && idx.scalar_type() == at::kLong && y_out.scalar_type() == at::kLong,
+              what, ": int64 labels / indices");
+  TORCH_CHECK(table.scalar_type() == at::kFloat && table.numel() == 256, what, ": table must be fp32 [256]");
+  const int64_t N = src.size(0), R = src.size(1), rows = y_out.numel();
+  TORCH_CHECK(R > 0 && R % 16 == 0, what, ": the row length must be a multiple of 16 bytes");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(src.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(x_out.data_ptr()) % 16 == 0, what, ": src / x_out must be 16-byte aligned");
+  TORCH_CHECK(rows > 0 && rows <= INT32_MAX && x_out.numel() == rows * R, what, ": x_out must be [rows, R]");
+  TORCH_CHECK(idx.numel() > 0 && labels.numel() == N, what, ": idx / labels");
+  TORCH_CHECK(start >= 0, what, ": start must not be negative");
+  uint32_t* cnt = nullptr;
+  if (counter != nullptr) {
+    TORCH_CHECK(counter->is_cuda() && counter->scalar_type() == at::kInt && counter->numel() >= 2 &&
+                counter->is_contiguous(), what, ": counter must be a device int32[2]");
+    cnt = reinterpret_cast<uint32_t*>(counter->data_ptr<int>());
+  }
+  check(pde::gather_rows_u8(src.data_ptr<uint8_t>(), labels.data_ptr<int64_t>(), idx.data_ptr<int64_t>(), idx.numel(),
+                            table.data_ptr<float>(), cnt, start, static_cast<int>(rows), static_cast<int>(R),
+                            x_out.data_ptr<float>(), y_out.data_ptr<int64_t>(), cur_stream()),
+        what);
+}
+
+void gather_rows_u8(const Tensor& src, const Tensor& labels, const Tensor& idx, const Tensor& table, Tensor& x_out,
+                    Tensor& y_out, int64_t start) {
+  gather_rows_u8_impl("gather_rows_u8", src, labels, idx, table, nullptr, x_out, y_out, start);
+}
+
+void gather_rows_u8_counter(const Tensor& src, const Tensor& labels, const Tensor& idx, const Tensor& table,
+                            Tensor& counter, Tensor& x_out, Tensor& y_out) {
+  gather_rows_u8_impl("gather_rows_u8_counter", src, labels, idx, table, &counter, x_out, y_out, 0);
+}
+
 // (mean cross-entropy loss, d loss / d logits as bf16) in one launch.  dx_out: a [B, >= V] bf16 row view to
 // write d logits into (its columns past V are left as they are, e.g. the zero padding of a K = 16 operand).
 std::vector<Tensor> ce_fused(const Tensor& x, const Tensor& tgt, const optional<Tensor>& dx_out) {
@@ -1543,6 +1582,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cast_rows_ones", &cast_rows_ones);
   m.def("gather_rows_counter", &gather_rows_counter, py::arg("src"), py::arg("labels"), py::arg("idx"),
         py::arg("counter"), py::arg("x_out"), py::arg("y_out"));
+  m.def("gather_rows_u8", &gather_rows_u8, py::arg("src_u8"), py::arg("labels"), py::arg("idx"), py::arg("table"),
+        py::arg("x_out"), py::arg("y_out"), py::arg("start") = 0);
+  m.def("gather_rows_u8_counter", &gather_rows_u8_counter, py::arg("src_u8"), py::arg("labels"), py::arg("idx"),
+        py::arg("table"), py::arg("counter"), py::arg("x_out"), py::arg("y_out"));
   m.def("ce_bwd", &ce_bwd);
   m.def("log_softmax_fwd", &log_softmax_fwd);
   m.def("log_softmax_bwd", &log_softmax_bwd);

@@ -259,6 +259,12 @@ int bn_reserve_headroom(int blocks);
 // fp32 / labels [N] into dst / ydst (elastic/rewire.py: the per-replay batch gather inside the captured graph)
 hipError_t gather_rows_counter(const float* src, const int64_t* labels, const int64_t* idx, int64_t n_idx,
                                uint32_t* counter, int rows, int row_elems, float* dst, int64_t* ydst, hipStream_t s);
+// The same gather from a uint8 dataset src [N, row_bytes] (row_bytes % 16 == 0), expanded through table [256]
+// (fp32) into dst [rows, row_bytes] fp32: dst = table[src byte].  counter == nullptr: the slice starts at list
+// position `start`; else at counter[0] x rows, with gather_rows_counter's protocol (data/mnist.py).
+hipError_t gather_rows_u8(const uint8_t* src, const int64_t* labels, const int64_t* idx, int64_t n_idx,
+                          const float* table, uint32_t* counter, int64_t start, int rows, int row_bytes, float* dst,
+                          int64_t* ydst, hipStream_t s);
 int bn_headroom_reserved();  // CUs currently reserved for spinning side-stream kernels
 void bn_launch_stats(long* one_launch, long* multi_launch, int* last_grid, int* cap);
 hipError_t bn_fwd_train(const uint16_t* x, int P, int C, const float* gamma, const float* beta, float eps,

@@ -430,29 +430,22 @@ hipError_t relu_bwd_bf16(const uint16_t* dy, const uint16_t* y, uint16_t* dx, lo
 // replayed k times trains on k different slices of the epoch with no host work between replays (the host sets
 // the counter once per epoch / resume).  Every workgroup reads the counter before it counts itself done, so
 // the increment never races a read; counter[1] is the done count (re-zeroed by the last workgroup).
-__global__ __launch_bounds__(256) void k_gather_rows_counter(const float4* __restrict__ src,
-                                                             const int64_t* __restrict__ labels,
-                                                             const int64_t* __restrict__ idx, int64_t n_idx,
-                                                             uint32_t* counter, int rows, int row4,
-                                                             float4* __restrict__ dst, int64_t* __restrict__ ydst) {
+// The two halves of the counter protocol, shared by the fp32 and the uint8 gather.  gather_base: the first
+// list position of this launch, counter[0] x rows (counter == nullptr: the host's `start`), read by one lane
+// and handed to the workgroup through LDS -- its barrier also publishes whatever the caller wrote to LDS before.
+__device__ __forceinline__ int64_t gather_base(uint32_t* counter, int rows, int64_t start) {
   __shared__ int64_t s_base;
   if (threadIdx.x == 0)
-    s_base = static_cast<int64_t>(__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) * rows;
+    s_base = counter == nullptr ? start
+                                : static_cast<int64_t>(__hip_atomic_load(counter, __ATOMIC_RELAXED,
+                                                                         __HIP_MEMORY_SCOPE_AGENT)) * rows;
   __syncthreads();
-  const int64_t base = s_base;
-  const int64_t total = static_cast<int64_t>(rows) * row4;
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-  for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
-    const int64_t row = t / row4, c = t - row * row4;
-    int64_t k = base + row;
-    k = k < n_idx ? k : n_idx - 1;  // (the host only replays whole slices; never read past the list)
-    dst[t] = src[idx[k] * row4 + c];
-  }
-  for (int64_t row = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; row < rows; row += stride) {
-    int64_t k = base + row;
-    k = k < n_idx ? k : n_idx - 1;
-    ydst[row] = labels[idx[k]];
-  }
+  return s_base;
+}
+
+// gather_done: this workgroup is done (it read the counter in gather_base); the launch's last one re-zeroes the
+// done count and advances the replay counter.
+__device__ __forceinline__ void gather_done(uint32_t* counter) {
   __syncthreads();
   if (threadIdx.x == 0) {
     const uint32_t n = __hip_atomic_fetch_add(counter + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -463,6 +456,68 @@ __global__ __launch_bounds__(256) void k_gather_rows_counter(const float4* __res
   }
 }
 
+// Labels of the gathered rows; the list position is clamped to the last entry (the host only replays whole
+// slices; never read past the list).
+__device__ __forceinline__ void gather_labels(const int64_t* __restrict__ labels, const int64_t* __restrict__ idx,
+                                              int64_t n_idx, int64_t base, int rows, int64_t* __restrict__ ydst) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t row = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; row < rows; row += stride) {
+    int64_t k = base + row;
+    k = k < n_idx ? k : n_idx - 1;
+    ydst[row] = labels[idx[k]];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_gather_rows_counter(const float4* __restrict__ src,
+                                                             const int64_t* __restrict__ labels,
+                                                             const int64_t* __restrict__ idx, int64_t n_idx,
+                                                             uint32_t* counter, int rows, int row4,
+                                                             float4* __restrict__ dst, int64_t* __restrict__ ydst) {
+  const int64_t base = gather_base(counter, rows, 0);
+  const int64_t total = static_cast<int64_t>(rows) * row4;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
+    const int64_t row = t / row4, c = t - row * row4;
+    int64_t k = base + row;
+    k = k < n_idx ? k : n_idx - 1;
+    dst[t] = src[idx[k] * row4 + c];
+  }
+  gather_labels(labels, idx, n_idx, base, rows, ydst);
+  gather_done(counter);
+}
+
+// The same gather from a uint8 dataset (data/mnist.py: the IDX bytes resident in HBM), expanded to the
+// normalised fp32 batch on the way: dst = table[src byte], table = the 256 possible normalised pixels (staged in
+// LDS, so the result is the host's arithmetic bit for bit under any compile flags).  One lane takes 16 source
+// bytes (one 16-byte load) and writes them as four 16-byte stores: 64 contiguous bytes per lane, 4 KiB per
+// wave.  A row is row16 such chunks, so rows straddle waves and workgroups.  counter == nullptr: the slice starts
+// at `start` and no counter is touched (gather_rows_u8); else the counter protocol above.  256 threads.
+__global__ __launch_bounds__(256) void k_gather_rows_u8(const uint4* __restrict__ src,
+                                                        const int64_t* __restrict__ labels,
+                                                        const int64_t* __restrict__ idx, int64_t n_idx,
+                                                        const float* __restrict__ table, uint32_t* counter,
+                                                        int64_t start, int rows, int row16,
+                                                        float4* __restrict__ dst, int64_t* __restrict__ ydst) {
+  __shared__ float s_table[256];
+  s_table[threadIdx.x] = table[threadIdx.x];
+  const int64_t base = gather_base(counter, rows, start);  // (its barrier covers s_table)
+  const int64_t total = static_cast<int64_t>(rows) * row16;
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; t < total; t += stride) {
+    const int64_t row = t / row16, c = t - row * row16;
+    int64_t k = base + row;
+    k = k < n_idx ? k : n_idx - 1;
+    const uint4 v = src[idx[k] * row16 + c];
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)  // little-endian: byte 0 of the word is the first pixel
+      dst[t * 4 + j] = make_float4(s_table[w[j] & 255u], s_table[(w[j] >> 8) & 255u], s_table[(w[j] >> 16) & 255u],
+                                   s_table[w[j] >> 24]);
+  }
+  gather_labels(labels, idx, n_idx, base, rows, ydst);
+  if (counter != nullptr) gather_done(counter);
+}
+
 hipError_t gather_rows_counter(const float* src, const int64_t* labels, const int64_t* idx, int64_t n_idx,
                                uint32_t* counter, int rows, int row_elems, float* dst, int64_t* ydst, hipStream_t s) {
   if (rows <= 0 || row_elems % 4 != 0) return hipErrorInvalidValue;
@@ -471,6 +526,18 @@ hipError_t gather_rows_counter(const float* src, const int64_t* labels, const in
   const int grid = static_cast<int>(std::min<int64_t>(2048, (total + 255) / 256));
   hipLaunchKernelGGL(k_gather_rows_counter, dim3(grid), dim3(256), 0, s, reinterpret_cast<const float4*>(src), labels,
                      idx, n_idx, counter, rows, row4, reinterpret_cast<float4*>(dst), ydst);
+  return hipGetLastError();
+}
+
+hipError_t gather_rows_u8(const uint8_t* src, const int64_t* labels, const int64_t* idx, int64_t n_idx,
+                          const float* table, uint32_t* counter, int64_t start, int rows, int row_bytes, float* dst,
+                          int64_t* ydst, hipStream_t s) {
+  if (rows <= 0 || row_bytes <= 0 || row_bytes % 16 != 0 || n_idx <= 0 || start < 0) return hipErrorInvalidValue;
+  const int row16 = row_bytes / 16;
+  const int64_t total = static_cast<int64_t>(rows) * row16;
+  const int grid = static_cast<int>(std::min<int64_t>(2048, (total + 255) / 256));
+  hipLaunchKernelGGL(k_gather_rows_u8, dim3(grid), dim3(256), 0, s, reinterpret_cast<const uint4*>(src), labels, idx,
+                     n_idx, table, counter, start, rows, row16, reinterpret_cast<float4*>(dst), ydst);
   return hipGetLastError();
 }
 

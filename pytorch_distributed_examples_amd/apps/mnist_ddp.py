@@ -13,7 +13,8 @@ after every epoch (:117-130; we also print the all-reduced global accuracy, Q6),
 lines, and ``Execution time``.
 
 MI355X-first differences: RCCL (``nccl``) over xGMI on GPUs -- gloo on CPU -- with the xGMI bucket
-policy; bf16 MFMA kernels; HBM-resident synthetic MNIST; atomic snapshot by global rank 0 only;
+policy; bf16 MFMA kernels; HBM-resident synthetic MNIST, or with ``--data_dir`` the MNIST IDX
+files held in HBM as bytes (:mod:`..data.mnist`); atomic snapshot by global rank 0 only;
 ``--model cnn`` runs BASELINE config 1's CNN through the same plumbing; ``--rewire`` keeps the worker alive
 across membership changes (in-process RCCL communicator re-wire, :mod:`..elastic.rewire`).
 
@@ -38,7 +39,7 @@ import time
 import torch
 
 from ..data.loader import ShardedLoader
-from ..data.synthetic import mnist_splits
+from ..data.mnist import mnist_datasets
 from ..elastic import fault
 from ..elastic.snapshot import load_snapshot, save_snapshot
 from ..ops import functional as OF
@@ -50,8 +51,8 @@ from ..utils import config as rtconfig
 from ..utils.config import add_runtime_args
 
 
-def load_train_objs(model_name: str, device, train_size: int, test_size: int):
-    train_set, test_set = mnist_splits(device=device, train=train_size, test=test_size)
+def load_train_objs(model_name: str, device, train_size: int, test_size: int, data_dir=None):
+    train_set, test_set = mnist_datasets(device, train_size, test_size, data_dir)
     if model_name == "cnn":
         from ..models.cnn import Net
 
@@ -131,7 +132,8 @@ class Trainer:
                     self.mega = MegaMLP(self.model, self.optimizer, xgmi=xa)
         else:
             self.ddp = DistributedDataParallel(self.model, **(ddp_kwargs or {}))
-        if (self.fused is not None or self.fmlp is not None) and hasattr(train_data.dataset, "images") and \
+        whole = hasattr(train_data.dataset, "images") or hasattr(train_data.dataset, "images_u8")
+        if (self.fused is not None or self.fmlp is not None) and whole and \
                 os.environ.get("PDE_EPOCH_GRAPH", "1") != "0":
             from ..utils.epoch_graph import ChunkedGraphs, EpochBatches
 
@@ -300,6 +302,9 @@ def main(argv=None):
     parser.add_argument("--snapshot_path", default="snapshot.pt")
     parser.add_argument("--train_size", type=int, default=60000)
     parser.add_argument("--test_size", type=int, default=10000)
+    parser.add_argument("--data_dir", default=None,
+                        help="directory with the four MNIST IDX files (plain or .gz; also DIR/MNIST/raw, DIR/raw); "
+                             "never downloaded.  Default: the synthetic set")
     parser.add_argument("--metrics", default=None, help="JSONL metrics file (rank 0)")
     parser.add_argument("--rewire", action="store_true",
                         help="survive membership changes in-process (RCCL communicator re-wire); launch with "
@@ -326,7 +331,7 @@ def main(argv=None):
         log = RankLogger(ctx.rank)
         metrics = MetricsWriter(args.metrics) if args.metrics and ctx.rank == 0 else None
         train_set, test_set, model, make_opt, criterion = load_train_objs(args.model, ctx.device, args.train_size,
-                                                                          args.test_size)
+                                                                          args.test_size, args.data_dir)
         train_data = ShardedLoader(train_set, args.batch_size, ctx.world_size, ctx.rank, shuffle=True)
         test_data = ShardedLoader(test_set, args.batch_size, ctx.world_size, ctx.rank, shuffle=False)
         trainer = Trainer(ctx, model, train_data, test_data, make_opt, criterion, args.save_every,

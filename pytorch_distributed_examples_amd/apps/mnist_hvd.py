@@ -25,7 +25,7 @@ import torch
 
 from .. import hvd
 from ..data.loader import ShardedLoader
-from ..data.synthetic import mnist_splits
+from ..data.mnist import mnist_datasets
 from ..models.cnn import Net
 from ..ops import functional as OF
 from ..ops.optim import FusedSGD
@@ -41,6 +41,9 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=1024)
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--train-size", type=int, default=60000)
+    ap.add_argument("--data-dir", default=None,
+                    help="directory with the four MNIST IDX files (plain or .gz; also DIR/MNIST/raw, DIR/raw); never "
+                         "downloaded.  Default: the synthetic set")
     ap.add_argument("--device", default="auto", choices=["auto", "cpu", "gpu"])
     ap.add_argument("--log-interval", type=int, default=5)
     ap.add_argument("--fused", action="store_true", help="fused whole-network training kernel (GPU; the default)")
@@ -55,7 +58,7 @@ def main(argv=None):
 
     hvd.init(device="cpu" if args.device == "cpu" else None)
     dev = hvd.core._ctx.device
-    train_set, _ = mnist_splits(device=dev, train=args.train_size, test=16)
+    train_set, _ = mnist_datasets(dev, args.train_size, 16, args.data_dir)
     loader = ShardedLoader(train_set, args.batch_size, hvd.size(), hvd.rank(), shuffle=True)
 
     model = Net().to(dev)

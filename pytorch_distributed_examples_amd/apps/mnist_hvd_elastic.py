@@ -28,7 +28,7 @@ import torch
 
 from .. import hvd
 from ..data.loader import ShardedLoader
-from ..data.synthetic import mnist_splits
+from ..data.mnist import mnist_datasets
 from ..elastic import fault
 from ..models.cnn import Net
 from ..ops import functional as OF
@@ -45,6 +45,9 @@ def main(argv=None):
     ap.add_argument("--batch-size", type=int, default=128)
     ap.add_argument("--train-size", type=int, default=60000)
     ap.add_argument("--test-size", type=int, default=10000)
+    ap.add_argument("--data-dir", default=None,
+                    help="directory with the four MNIST IDX files (plain or .gz; also DIR/MNIST/raw, DIR/raw); never "
+                         "downloaded.  Default: the synthetic set")
     ap.add_argument("--device", default="auto", choices=["auto", "cpu", "gpu"])
     ap.add_argument("--layers", action="store_true", help="GPU: the autograd layer path instead of the fused step")
     ap.add_argument("--no-graph", action="store_true", help="GPU fused step without hipGraph capture")
@@ -57,7 +60,7 @@ def main(argv=None):
 
     hvd.init(device="cpu" if args.device == "cpu" else None)
     dev = hvd.core._ctx.device
-    train_set, test_set = mnist_splits(device=dev, train=args.train_size, test=args.test_size)
+    train_set, test_set = mnist_datasets(dev, args.train_size, args.test_size, args.data_dir)
 
     model = Net().to(dev)
     optimizer = FusedAdamW(model.parameters(), lr=lr / math.sqrt(hvd.size()))

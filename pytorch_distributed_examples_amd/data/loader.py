@@ -5,6 +5,8 @@ batches are built by ONE index gather on the device instead of per-sample collat
 processes -- on an MI355X the 188 MB MNIST train set simply lives in HBM.  Sharding and shuffling are
 exactly ``torch.utils.data.distributed.DistributedSampler``'s (same seed / epoch semantics, padding to
 an equal number of samples per rank), so ``len(loader)`` and per-rank sample sets match the reference.
+A dataset held as bytes (``images_u8``: :class:`.mnist.MNIST`) builds the same batches through its own
+``gather``, which expands them to normalised fp32 on the way.
 
 ``start_batch`` skips whole batches without loading them (quirk Q10: the Horovod-elastic reference loads
 and discards skipped batches).
@@ -34,11 +36,14 @@ class ShardedLoader:
     def __iter__(self):
         idx = torch.tensor(list(iter(self.sampler)), dtype=torch.long)
         images, labels = getattr(self.dataset, "images", None), getattr(self.dataset, "labels", None)
-        dev = images.device if images is not None else torch.device("cpu")
+        u8 = getattr(self.dataset, "images_u8", None)  # a byte dataset (data/mnist.py): its gather expands to fp32
+        dev = u8.device if u8 is not None else images.device if images is not None else torch.device("cpu")
         idx_dev = idx.to(dev)
         for b in range(self.start_batch, len(self)):
             sl = idx_dev[b * self.batch_size:(b + 1) * self.batch_size]
-            if images is not None:
+            if u8 is not None:
+                yield self.dataset.gather(sl)
+            elif images is not None:
                 yield images.index_select(0, sl), labels.index_select(0, sl)
             else:
                 items = [self.dataset[int(i)] for i in sl.tolist()]

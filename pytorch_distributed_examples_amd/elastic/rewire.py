@@ -473,7 +473,7 @@ def run_elastic(args):
     else:
         dev = torch.device("cpu")
     train_set, test_set, model, make_opt, criterion = load_train_objs(args.model, dev, args.train_size,
-                                                                      args.test_size)
+                                                                      args.test_size, getattr(args, "data_dir", None))
     model = model.to(dev)
     optimizer = make_opt(model.parameters())
     pos = {"epoch": 0, "seen": 0}  # samples of the current epoch consumed by the whole group
@@ -695,7 +695,7 @@ def run_elastic_fused(args, report=None):
     import time as _time
 
     from ..data.loader import ShardedLoader
-    from ..data.synthetic import mnist_splits
+    from ..data.mnist import mnist_datasets
     from ..elastic.snapshot import save_snapshot
     from ..models.cnn import Net
     from ..models.cnn_fused import FusedCNN
@@ -733,7 +733,9 @@ def run_elastic_fused(args, report=None):
     # (indices wrap around the real samples) so its timed window never straddles an epoch boundary
     real_train = int(getattr(args, "train_size", 60000))
     virt_train = int(getattr(args, "virtual_train_size", 0) or real_train)
-    train_set, test_set = mnist_splits(device=dev, train=real_train, test=int(getattr(args, "test_size", 10000)))
+    train_set, test_set = mnist_datasets(dev, real_train, int(getattr(args, "test_size", 10000)),
+                                         getattr(args, "data_dir", None))
+    as_bytes = hasattr(train_set, "images_u8")  # the IDX files, held as uint8: the gathers expand to fp32
     train_view = train_set
     if virt_train != real_train:
         class _Virtual:  # a longer epoch over the same samples (ShardedLoader only needs len())
@@ -759,6 +761,9 @@ def run_elastic_fused(args, report=None):
     pid = os.getpid()
 
     def gather(idx, lo, hi, xo, yo):
+        if as_bytes:
+            train_set.gather(idx, out=(xo, yo), start=lo, rows=hi - lo)
+            return
         sl = idx[lo:hi]  # (already reduced modulo the real sample count)
         torch.index_select(train_set.images, 0, sl, out=xo)
         torch.index_select(train_set.labels, 0, sl, out=yo)
@@ -889,8 +894,12 @@ def run_elastic_fused(args, report=None):
                             (graph is not None or pos["step"] > round_step0):
                         if graph is None:  # after >= 1 eager step of this round initialised everything
                             def gather_slots():
-                                C_.gather_rows_counter(train_set.images, train_set.labels, idx_buf, counter, xbuf,
-                                                       ybuf)
+                                if as_bytes:
+                                    C_.gather_rows_u8_counter(train_set.images_u8, train_set.labels, idx_buf,
+                                                              train_set.table, counter, xbuf, ybuf)
+                                else:
+                                    C_.gather_rows_counter(train_set.images, train_set.labels, idx_buf, counter, xbuf,
+                                                           ybuf)
                             graph = CapturedSteps(train_step, slots, warmup=0, prologue=gather_slots).capture()
                         if at != b // G:
                             counter.copy_(torch.tensor([b // G, 0], dtype=torch.int32))

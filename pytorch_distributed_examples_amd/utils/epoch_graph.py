@@ -45,16 +45,23 @@ def sampler_indices(s) -> torch.Tensor:
 
 
 class EpochBatches:
-    """Fixed-address, per-epoch permuted copy of one rank's shard of a whole-tensor dataset (``images``/``labels``)."""
+    """Fixed-address, per-epoch permuted copy of one rank's shard of a whole-tensor dataset (``images``/``labels``,
+    or ``images_u8``/``labels`` with a ``gather`` that expands the bytes: the copy is fp32 either way)."""
 
     def __init__(self, loader):
         self.loader = loader
         ds = loader.dataset
-        self.images, self.labels = ds.images, ds.labels
+        # a byte dataset (``images_u8``: data/mnist.py) is expanded to fp32 by its own gather; else ``images`` is fp32
+        self.u8 = ds if hasattr(ds, "images_u8") else None
+        self.images, self.labels = (None if self.u8 is not None else ds.images), ds.labels
+        self.device = ds.images_u8.device if self.u8 is not None else ds.images.device
         self.batch_size = loader.batch_size
         n = len(loader.sampler)
         self.n = n
-        self.x = torch.empty((n,) + tuple(self.images.shape[1:]), dtype=self.images.dtype, device=self.images.device)
+        if self.u8 is not None:
+            self.x = torch.empty((n,) + tuple(ds.sample_shape), dtype=torch.float32, device=self.device)
+        else:
+            self.x = torch.empty((n,) + tuple(self.images.shape[1:]), dtype=self.images.dtype, device=self.device)
         self.y = torch.empty((n,) + tuple(self.labels.shape[1:]), dtype=self.labels.dtype, device=self.labels.device)
         self._last = None
         self._ready: dict = {}  # epoch -> its permutation, computed ahead (prepare)
@@ -77,12 +84,15 @@ class EpochBatches:
             order = sampler_indices(self.loader.sampler)
         if self._last is not None and torch.equal(order, self._last):
             return
-        if self.images.is_cuda:
-            idx = (order if order.is_pinned() else order.pin_memory()).to(self.images.device, non_blocking=True)
+        if self.device.type == "cuda":
+            idx = (order if order.is_pinned() else order.pin_memory()).to(self.device, non_blocking=True)
         else:
             idx = order
-        torch.index_select(self.images, 0, idx, out=self.x)
-        torch.index_select(self.labels, 0, idx, out=self.y)
+        if self.u8 is not None:
+            self.u8.gather(idx, out=(self.x, self.y))
+        else:
+            torch.index_select(self.images, 0, idx, out=self.x)
+            torch.index_select(self.labels, 0, idx, out=self.y)
         self._last = order
 
     def prepare(self, epoch: int) -> None:
@@ -91,7 +101,7 @@ class EpochBatches:
         cur = s.epoch
         s.set_epoch(epoch)
         try:
-            self._ready[epoch] = sampler_indices(s).pin_memory() if self.images.is_cuda else sampler_indices(s)
+            self._ready[epoch] = sampler_indices(s).pin_memory() if self.device.type == "cuda" else sampler_indices(s)
         finally:
             s.set_epoch(cur)
 
