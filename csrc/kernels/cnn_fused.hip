@@ -522,10 +522,49 @@ __device__ __forceinline__ float pool4(const f32x4& v, int& am) {
   return m;
 }
 
+// conv1 tile ownership.  A tile is 4 consecutive pooling cells of one cell row (P1 / 4 tiles per row, MT1 per
+// image).  Wave w owns NT1 CONTIGUOUS tiles: image w / P1_WI, the P1_WR whole cell rows from (w % P1_WI) * P1_WR,
+// its tile u being row u / P1_TR of those, cells 4 (u % P1_TR) .. +3.  Only the wave's first tile depends on the
+// wave id; tile u lies a compile-time distance from it in x, r1n, r1 and a1 alike.  (With the tiles dealt round
+// robin, wid + u NW, none of that folded: every tile carried its own scalar tile / 36, t4 / 3 and remainder
+// chains and its own vector address adds, ~650 issued instructions per wave around 9 MFMAs.)
+static_assert(P1 % 4 == 0 && MT1 * 4 == NC1, "conv1 tiles: 4 cells of one row");
+static_assert((NI * MT1) % NW == 0, "every wave runs the same number of conv1 tiles");
+constexpr int NT1 = NI * MT1 / NW;  // 9 tiles per wave
+constexpr int P1_TR = P1 / 4;       // 3 tiles per cell row
+static_assert(MT1 % NT1 == 0, "conv1: a wave's tiles lie in one image");
+static_assert(NT1 % P1_TR == 0, "conv1: a wave's tiles are whole cell rows");
+constexpr int P1_WI = MT1 / NT1;    // 4 waves per image
+constexpr int P1_WR = NT1 / P1_TR;  // 3 cell rows per wave
+struct P1Tile {
+  int im, py, px0;  // image, cell row, first cell column
+};
+__host__ __device__ constexpr P1Tile p1_tile(int w, int u) {
+  return {w / P1_WI, (w % P1_WI) * P1_WR + u / P1_TR, (u % P1_TR) * 4};
+}
+__host__ __device__ constexpr bool p1_map_ok() {  // every (image, tile) on exactly one (wave, u)
+  for (int tile = 0; tile < NI * MT1; ++tile) {
+    int n = 0;
+    for (int w = 0; w < NW; ++w)
+      for (int u = 0; u < NT1; ++u) {
+        const P1Tile q = p1_tile(w, u);
+        if (q.im < 0 || q.im >= NI || q.py < 0 || q.py >= P1 || q.px0 < 0 || q.px0 + 4 > P1) return false;
+        if (q.im * MT1 + q.py * P1_TR + q.px0 / 4 == tile) ++n;
+      }
+    if (n != 1) return false;
+  }
+  return true;
+}
+static_assert(p1_map_ok(), "conv1 wave map: the 16 waves cover each of the NI * MT1 tiles exactly once");
+
 // ---- P1: conv1 (MFMA, M = (cell, tap), K = (ky, kx6) 30 -> 32, N = co) + maxpool2 + relu ----------
 // K runs over 6-wide kernel rows (kx = 5 has zero weight): every k pair (kx even) is two consecutive
 // pixels, read as ONE aligned 4-byte LDS load -- from x when the window starts on an even column (dx = 0),
 // from the shifted copy x1 otherwise: 4 gathers per fragment instead of 8.
+// Addresses: each lane forms its 4 gather bases and its 3 store bases (r1n, r1, a1) ONCE, at the wave's first
+// tile (p1_tile above); tile u's distance from it is a constant that rides in the LDS instruction's offset
+// field, and pairs of gathers merge into ds_read2_b32.  The lane -> (cell, tap) mapping inside a tile, and
+// with it the bank pattern of one gather instruction (2.75 LDS cycles, XP above), is the same for every tile.
 template <bool TRAIN, class Smem>
 __device__ __forceinline__ void cnn_p1(Smem& S, int lane, int wid) {
   static_assert((offsetof(Smem, x1) - offsetof(Smem, x)) / 4 % 32 == 9, "x1 bank offset from x (P1 gathers)");
@@ -540,45 +579,62 @@ __device__ __forceinline__ void cnn_p1(Smem& S, int lane, int wid) {
   const u16x8 bw = S.w1f[lane];
   const int tap = lr & 3, dy = tap >> 1, dx = tap & 1;
   const uint16_t* xsrc = dx ? &S.x1[0][0] - 1 : &S.x[0][0];  // x1[i - 1] = x[i]: odd starts become even
-  // a tile is 4 consecutive pooling cells of one cell row (12 % 4 == 0): image, cell row and first column
-  // are wave-uniform (scalar), the lane adds its cell (lr >> 2) and tap -- no per-lane division
-  static_assert(P1 % 4 == 0 && MT1 * 4 == NC1, "conv1 tiles: 4 cells of one row");
-  const uint16_t* xlane = xsrc + dy * XP + 2 * (lr >> 2) + dx;
-  auto gather = [&](int tile, u16x8& a) {
-    const int im = tile / MT1, t4 = tile - im * MT1, py = t4 / (P1 / 4), px0 = (t4 - py * (P1 / 4)) * 4;
-    const uint16_t* xb = xlane + im * NXP + 2 * py * XP + 2 * px0;
-    u32x4 v;
+  // the wave's first tile: image and cell row are wave-uniform (scalar, px0 = 0); the lane adds its cell
+  // (lr >> 2), its tap and its 4 k pairs -- no per-lane division, nothing per tile
+  const P1Tile w0 = p1_tile(wid, 0);
+  const uint16_t* xlane = xsrc + dy * XP + 2 * (lr >> 2) + dx + w0.im * NXP + 2 * w0.py * XP;
+  const uint16_t* xb[4];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) v[p] = *reinterpret_cast<const uint32_t*>(xb + koff[p]);
-    a = __builtin_bit_cast(u16x8, v);
-  };
-  static_assert((NI * MT1) % NW == 0, "every wave runs the same number of conv1 tiles");
-  constexpr int NT1 = NI * MT1 / NW;  // 9 tiles per wave
+  for (int p = 0; p < 4; ++p) xb[p] = xlane + koff[p];
   // all of the wave's gathers first, then its MFMAs, then the epilogues: no tile waits on another's LDS
   // round trip (a one-tile-ahead pipeline measured 3.0 us for this loop, r4p)
   u16x8 ag[NT1];
 #pragma unroll
-  for (int u = 0; u < NT1; ++u) gather(wid + u * NW, ag[u]);
+  for (int u = 0; u < NT1; ++u) {
+    const P1Tile q = p1_tile(0, u);  // tile u relative to the wave's first: constants once unrolled
+    const int xo = 2 * q.py * XP + 2 * q.px0;
+    u32x4 v;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) v[p] = *reinterpret_cast<const uint32_t*>(xb[p] + xo);
+    ag[u] = __builtin_bit_cast(u16x8, v);
+  }
   f32x4 accs[NT1];
 #pragma unroll
   for (int u = 0; u < NT1; ++u) accs[u] = mfma(ag[u], bw, f32x4{0.f, 0.f, 0.f, 0.f});
-  const float bias1 = lr < C1 ? S.b1[lr] : 0.f;
+  const int co = lr;  // rows (lg*4 + r) = taps r of cell c0 + lg
+  // (a clamped index and a select: no exec region around one LDS read)
+  const float b1v = S.b1[min(co, C1 - 1)];
+  const float bias1 = co < C1 ? b1v : 0.f;
+  const int cw = w0.py * P1 + lg;  // the lane's cell of the wave's first tile; tile u's is q.py * P1 + q.px0 further
+  uint16_t* r1n = &S.r1n[w0.im][cw][co];
+  uint16_t rr[NT1];
+  int am[NT1];
 #pragma unroll
   for (int u = 0; u < NT1; ++u) {
-    const int tile = wid + u * NW;
-    const int im = tile / MT1, c0 = (tile - im * MT1) * 4;
-    const int co = lr;  // rows (lg*4 + r) = taps r of cell c0 + lg
-    int am;
-    const float m = pool4(accs[u], am);
-    // lanes co >= C1: w1f's columns and bias1 are zero there, so r == 0 -- r1n's ci padding gets its zeros;
-    // their r1 / a1 stores are masked off (exec, no per-lane address selects)
-    const uint16_t r = f2bf(fmaxf(m + bias1, 0.f));
-    S.r1n[im][c0 + lg][co] = r;
+    const P1Tile q = p1_tile(0, u);
+    const float m = pool4(accs[u], am[u]);
+    // lanes co >= C1: w1f's columns and bias1 are zero there, so r == 0 -- r1n's ci padding gets its zeros
+    rr[u] = f2bf(fmaxf(m + bias1, 0.f));
+    r1n[(q.py * P1 + q.px0) * C1P] = rr[u];
     if constexpr (TRAIN) {
-      if (r == 0) am = AM_DEAD;  // relu-dead: P7b's epilogue and P9 read the mask from a1
-      if (co < C1) {
-        S.r1[im][co * RP16 + c0 + lg] = r;
-        S.a1[im][co * RP8 + c0 + lg] = static_cast<unsigned char>(am);
+      if (rr[u] == 0) am[u] = AM_DEAD;  // relu-dead: P7b's epilogue and P9 read the mask from a1
+      // the tap is a VGPR value HERE: left alone, the compiler sinks the selects into the store region below
+      // and keeps the 9 tiles' 27 compare masks (54 SGPRs) live up to it, which spills the kernel's long-lived
+      // scalars to VGPR lanes
+      asm volatile("" : "+v"(am[u]));
+    }
+  }
+  if constexpr (TRAIN) {
+    // the backward's copies, all tiles under ONE exec region: lanes co >= C1 have none (exec, no per-lane
+    // address selects)
+    if (co < C1) {
+      uint16_t* r1 = &S.r1[w0.im][co * RP16 + cw];
+      unsigned char* a1 = &S.a1[w0.im][co * RP8 + cw];
+#pragma unroll
+      for (int u = 0; u < NT1; ++u) {
+        const P1Tile q = p1_tile(0, u);
+        r1[q.py * P1 + q.px0] = rr[u];
+        a1[q.py * P1 + q.px0] = static_cast<unsigned char>(am[u]);
       }
     }
   }

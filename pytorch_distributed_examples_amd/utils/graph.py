@@ -22,6 +22,9 @@ captured step is a complete training step (forward, backward, all-reduce, optimi
 """
 from __future__ import annotations
 
+import contextlib
+import gc
+
 import torch
 
 from ..ops import functional as OF
@@ -37,6 +40,24 @@ def upload(g: torch.cuda.CUDAGraph) -> None:
         torch.cuda.synchronize()
     except Exception:  # noqa: BLE001 - an optimisation only
         pass
+
+
+@contextlib.contextmanager
+def collector_off():
+    """Around a graph capture: collect cyclic garbage now, then keep the cycle collector off until the capture ends.
+
+    A dead ``torch.cuda.CUDAGraph`` that sits in a reference cycle (a trainer and its graph runner hold each other)
+    is destroyed by the collector whenever it happens to run next.  On ROCm that destructor synchronises the device;
+    inside another graph's capture the call is refused, the error leaves the destructor as an exception and the
+    process aborts.  (``torch.cuda.graph`` itself no longer collects on entry.)"""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class CapturedStep:
@@ -58,7 +79,7 @@ class CapturedStep:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
-        with OF.recompute_weight_copies():
+        with OF.recompute_weight_copies(), collector_off():
             with torch.cuda.graph(g):
                 self.static_out = self.step_fn(*self.static_inputs)
         torch.cuda.synchronize()
@@ -103,7 +124,7 @@ class CapturedSteps:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
-        with OF.recompute_weight_copies():
+        with OF.recompute_weight_copies(), collector_off():
             with torch.cuda.graph(g, pool=self._pool):
                 if self.prologue is not None:
                     self.prologue()
