@@ -1182,8 +1182,27 @@ Tensor cnn_train(const Tensor& images, const Tensor& tgt, const Tensor& params, 
                  double p_drop1, bool training, Tensor& grads, bool accumulate, const optional<Tensor>& gscale,
                  const optional<Tensor>& stamps, const optional<Tensor>& frag_buf, bool prep,
                  const optional<Tensor>& sgd_hp, int64_t stop_after, const optional<Tensor>& sgd_step,
-                 const optional<std::vector<int64_t>>& xgmi_view, double xscale) {
+                 const optional<std::vector<int64_t>>& xgmi_view, double xscale, int64_t opt_mode,
+                 const optional<Tensor>& opt_m, const optional<Tensor>& opt_v) {
   CHECK_IN(images); CHECK_IN(tgt); CHECK_IN(params); CHECK_IN(rng); CHECK_IN(grads);
+  // the stateful updates in the reduction (1 SGD + momentum / weight decay, 2 Adam, 3 AdamW): hyper-parameters,
+  // step words and flat state buffers shaped like params
+  TORCH_CHECK(opt_mode >= 0 && opt_mode <= 3, "cnn_train: opt_mode must be 0..3");
+  const bool have_m = opt_m.has_value() && opt_m->defined(), have_v = opt_v.has_value() && opt_v->defined();
+  if (opt_mode != 0) {
+    TORCH_CHECK(sgd_hp.has_value() && sgd_hp->defined() && sgd_step.has_value() && sgd_step->defined(),
+                "cnn_train: opt_mode != 0 needs sgd_hp and sgd_step");
+    TORCH_CHECK(sgd_step->is_cuda() && sgd_step->scalar_type() == at::kInt && sgd_step->numel() >= 2,
+                "cnn_train: opt_mode != 0 needs step int32[2]");
+    TORCH_CHECK(have_m, "cnn_train: opt_mode != 0 needs opt_m (momentum_buffer / exp_avg)");
+    TORCH_CHECK(opt_mode < 2 || have_v, "cnn_train: Adam / AdamW need opt_v (exp_avg_sq)");
+  }
+  for (const Tensor* t : {have_m ? &*opt_m : nullptr, have_v ? &*opt_v : nullptr}) {
+    if (t == nullptr) continue;
+    CHECK_IN(*t); CHECK_F32(*t);
+    TORCH_CHECK(t->numel() == pde::cnn_num_params() && t->device() == params.device(),
+                "cnn_train: optimiser state must be flat fp32 buffers shaped like params, on their device");
+  }
   pde::XgmiView xv{};
   const bool have_xv = xgmi_view.has_value();
   if (have_xv) {  // XgmiAllreduce.view(): base[8], state, timeout_ticks, flag_bytes, slot_bytes, rank, size, blocks,
@@ -1245,7 +1264,8 @@ Tensor cnn_train(const Tensor& images, const Tensor& tgt, const Tensor& params, 
                              prep ? 1 : 0, sgd_hp.has_value() && sgd_hp->defined() ? sgd_hp->data_ptr<float>() : nullptr,
                              static_cast<int>(stop_after),
                              sgd_step.has_value() && sgd_step->defined() ? sgd_step->data_ptr<int>() : nullptr,
-                             have_xv ? &xv : nullptr, static_cast<float>(xscale)),
+                             have_xv ? &xv : nullptr, static_cast<float>(xscale), static_cast<int>(opt_mode),
+                             f32(opt_m), f32(opt_v)),
         "cnn_train");
   return loss;
 }
@@ -1456,6 +1476,32 @@ void cnn_adamw(Tensor& params, const Tensor& grads, Tensor& m, Tensor& v, const 
         "cnn_adamw");
 }
 
+// The stateful updates over the flat CNN parameters + fragment refresh, one launch (FusedCNN.opt_step).  mode: the
+// optimiser kernels' (0 SGD with momentum / weight decay -- m: the momentum buffers, no v; 1 Adam; 2 AdamW)
+void cnn_opt(Tensor& params, const Tensor& grads, Tensor& m, const optional<Tensor>& v, const Tensor& hp, Tensor& frag,
+             Tensor& step, int64_t mode) {
+  CHECK_IN(params); CHECK_IN(grads); CHECK_IN(m); CHECK_IN(hp); CHECK_IN(frag);
+  CHECK_F32(params); CHECK_F32(grads); CHECK_F32(m); CHECK_F32(hp);
+  TORCH_CHECK(mode >= 0 && mode <= 2, "cnn_opt: mode must be 0..2");
+  const long n = pde::cnn_num_params();
+  TORCH_CHECK(params.numel() == n && grads.numel() == n && m.numel() == n, "cnn_opt: sizes");
+  const bool have_v = v.has_value() && v->defined();
+  TORCH_CHECK(mode == 0 || have_v, "cnn_opt: Adam / AdamW need v (exp_avg_sq)");
+  if (have_v) {
+    CHECK_IN(*v); CHECK_F32(*v);
+    TORCH_CHECK(v->numel() == n && v->device() == params.device(), "cnn_opt: v size / device");
+  }
+  TORCH_CHECK(m.device() == params.device() && grads.device() == params.device(), "cnn_opt: devices");
+  TORCH_CHECK(hp.numel() >= pde::HP_COUNT, "cnn_opt: hp");
+  TORCH_CHECK(frag.nbytes() >= pde::cnn_frag_bytes() && reinterpret_cast<uintptr_t>(frag.data_ptr()) % 16 == 0,
+              "cnn_opt: frag size / alignment");
+  TORCH_CHECK(step.is_cuda() && step.scalar_type() == at::kInt && step.numel() >= 2, "cnn_opt: step int32[2]");
+  check(pde::cnn_opt_fused(params.data_ptr<float>(), grads.data_ptr<float>(), m.data_ptr<float>(), f32(v),
+                           hp.data_ptr<float>(), frag.data_ptr(), step.data_ptr<int>(), static_cast<int>(mode),
+                           cur_stream()),
+        "cnn_opt");
+}
+
 void cnn_sgd(Tensor& params, const Tensor& grads, const Tensor& hp, Tensor& frag, const optional<Tensor>& step) {
   CHECK_IN(params); CHECK_IN(grads); CHECK_IN(hp); CHECK_IN(frag);
   CHECK_F32(params); CHECK_F32(grads); CHECK_F32(hp);
@@ -1476,7 +1522,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("p_drop2"), py::arg("p_drop1"), py::arg("training"), py::arg("grads"), py::arg("accumulate"),
         py::arg("gscale") = py::none(), py::arg("stamps") = py::none(), py::arg("frag") = py::none(),
         py::arg("prep") = true, py::arg("sgd_hp") = py::none(), py::arg("stop_after") = -1,
-        py::arg("sgd_step") = py::none(), py::arg("xgmi_view") = py::none(), py::arg("xscale") = 1.0);
+        py::arg("sgd_step") = py::none(), py::arg("xgmi_view") = py::none(), py::arg("xscale") = 1.0,
+        py::arg("opt_mode") = 0, py::arg("opt_m") = py::none(), py::arg("opt_v") = py::none());
+  m.def("cnn_opt", &cnn_opt, py::arg("params"), py::arg("grads"), py::arg("m"), py::arg("v"), py::arg("hp"),
+        py::arg("frag"), py::arg("step"), py::arg("mode"));
   m.def("mlp_train_grid", &mlp_train_grid_py);
   m.def("mlp_train", &mlp_train, py::arg("x"), py::arg("y"), py::arg("w"), py::arg("b"), py::arg("gw"), py::arg("gb"),
         py::arg("mw"), py::arg("vw"), py::arg("mb"), py::arg("vb"), py::arg("wbf"), py::arg("wtbf"), py::arg("act"),

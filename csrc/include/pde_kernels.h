@@ -321,7 +321,17 @@ hipError_t cnn_train_fused(const float* images, const int64_t* tgt, int B, float
                            float* loss_part, uint16_t* acts, int nwg, float* loss, float* grads, const float* gscale,
                            int accumulate, hipStream_t s, unsigned long long* stamps = nullptr, int prep = 1,
                            const float* sgd_hp = nullptr, int stop_after = -1, int* sgd_step = nullptr,
-                           const XgmiView* xv = nullptr, float xscale = 1.f);
+                           const XgmiView* xv = nullptr, float xscale = 1.f, int opt_mode = 0,
+                           float* opt_m = nullptr, float* opt_v = nullptr);
+// opt_mode: the update fused into the slab reduction when sgd_hp != nullptr.  0 plain SGD (above); 1 SGD with
+// momentum and / or L2 weight decay; 2 Adam (L2); 3 AdamW -- the optimiser's own update function (optim_device.h)
+// on the final gradient, its state in flat fp32 buffers indexed like params: opt_m (momentum_buffer / exp_avg) and
+// opt_v (exp_avg_sq, modes 2 and 3).  The stateful modes need sgd_hp, sgd_step ({steps taken, arrival ticket})
+// and their state: hipErrorInvalidValue otherwise.
+// cnn_opt_fused: the same stateful updates (mode: 0 SGD + momentum / weight decay, 1 Adam, 2 AdamW) and the
+// fragment refresh as ONE launch after an all-reduce that ran outside the reduction kernel.
+hipError_t cnn_opt_fused(float* params, const float* grads, float* m, float* v, const float* hp, void* frag,
+                         int* step, int mode, hipStream_t s);
 // params -= lr * gscale * grads (plain SGD) and the matching fragment-image refresh, one launch (used
 // after the gradient all-reduce when world > 1).
 // 1 when the single-process fused tail's grid barrier timed out (PDE_CNN_FUSED_TAIL); reset clears it

@@ -1416,6 +1416,15 @@ __device__ __forceinline__ void sgd_update(float* params, float lr, float gsc, u
 // tile; role 0 also reduces the loss partials and advances the dropout RNG / SGD step counters), run by the
 // first RED_T threads of a block whose every thread calls it (block barriers inside).  Called by k_cnn_reduce
 // (one role per block) and, single process, by k_cnn_train's workgroups after a grid barrier.
+//
+// OPT: the update the role applies when hp != nullptr.  0: plain SGD (sgd_update above; role 0 counts the step);
+// 1: SGD with momentum and / or L2 weight decay; 2: Adam (L2); 3: AdamW -- optdev::update<OPT - 1> on the final
+// gradient, the optimiser's state in the flat buffers om (momentum_buffer / exp_avg) and ov (exp_avg_sq, OPT >= 2),
+// indexed like params and owned by the threads that own the weight.  These modes need the 1-based step: every
+// block reads step[0] + 1 at role entry (one thread, a shared word, published by the role's own barrier) and
+// arrives at the ticket in step[1] at its end; the last of gridDim.x arrivals stores the new count and clears the
+// ticket (k_cnn_adamw's protocol), so no block can read a count another block already advanced.
+template <int OPT>
 __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s_epoch, int* s_fail,
                                                 const float* __restrict__ slabs, int nwg,
                                                 const uint16_t* __restrict__ acts, const float* __restrict__ gscale,
@@ -1423,9 +1432,40 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
                                                 const float* __restrict__ loss_part, int B, float* __restrict__ loss,
                                                 unsigned long long* __restrict__ rng, float* __restrict__ params,
                                                 const float* __restrict__ hp, uint16_t* __restrict__ frag,
-                                                int* __restrict__ step, const XgmiView& xv, float xscale) {
+                                                int* __restrict__ step, const XgmiView& xv, float xscale,
+                                                float* __restrict__ om = nullptr, float* __restrict__ ov = nullptr) {
   const int tid = threadIdx.x;
   const bool act = tid < RED_T;  // (k_cnn_train's threads past RED_T only join the barriers)
+  int* s_stepw = nullptr;  // OPT != 0: the step being taken (1-based), one word per block
+  int step0 = 0;
+  if constexpr (OPT != 0) {
+    __shared__ int s_step;
+    s_stepw = &s_step;
+  }
+  // thread 0 requests the step count behind the first batch of operands (a vector load, like load_scalars') and
+  // parks it in the shared word next to the partial sums: the role's barrier there publishes it to the updaters
+  auto load_step = [&]() {
+    if constexpr (OPT != 0) {
+      int z = 0;
+      asm("" : "+v"(z));
+      if (tid == 0) step0 = step[z];
+    }
+  };
+  auto park_step = [&]() {
+    if constexpr (OPT != 0) {
+      if (tid == 0) *s_stepw = step0 + 1;
+    }
+  };
+  // the stateful update of parameter p (w0 / m0 / v0 loaded at the start of the role, g final) + fragment refresh
+  auto opt_update = [&](const optdev::Hyper& h, int p, float w0, float m0, float v0, float g) {
+    if constexpr (OPT != 0) {
+      optdev::update<OPT - 1>(h, w0, g, m0, v0);
+      params[p] = w0;
+      om[p] = m0;
+      if constexpr (OPT >= 2) ov[p] = v0;
+      write_frag(frag, p, w0);
+    }
+  };
   // world > 1 with a peer view: this block's gradients go through the one-shot xGMI exchange (stage to my
   // slot, flags, read all ranks' values in rank order, x xscale) before the store + SGD update
   const bool xchg = xv.size > 1;
@@ -1473,7 +1513,8 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
     for (int u = 0; u < 8; ++u)
       v8[u] = s4[static_cast<long>(min(sl + u * RED_LANES, nwg - 1)) * (NSLABP / 4) + SLAB_OFS / 4 + min(c4, NSLAB4 - 1)];
     load_scalars();
-    f32x4 w0 = a0, g0 = a0;
+    load_step();
+    f32x4 w0 = a0, g0 = a0, m0 = a0, v0 = a0;
     // (one shape for both column kinds, four dword loads: with a float4 load on a second path the two paths'
     // results share registers, and the compiler drains the slab loads before it overwrites them)
     if (owner) {
@@ -1481,6 +1522,12 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
       for (int j = 0; j < 4; ++j) {
         if (hp) w0[j] = params[pj[j]];
         if (accumulate) g0[j] = grads[pj[j]];
+        if constexpr (OPT != 0) {
+          if (hp) m0[j] = om[pj[j]];
+        }
+        if constexpr (OPT >= 2) {
+          if (hp) v0[j] = ov[pj[j]];
+        }
       }
     }
     {
@@ -1513,6 +1560,7 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
       for (; b < nwg; b += RED_LANES) a0 += s4[static_cast<long>(b) * (NSLABP / 4) + SLAB_OFS / 4 + c4];
     }
     if (act) part[sl * RED_COLS + col] = (a0 + a1) + (a2 + a3);
+    park_step();
     __syncthreads();
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     if (owner) {
@@ -1546,9 +1594,15 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
       } else {
         reinterpret_cast<f32x4*>(grads)[p4] = v;
       }
-      if (hp) {
+      if constexpr (OPT == 0) {
+        if (hp) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) sgd_update(params, lrate, gsc, frag, pj[j], w0[j], v[j]);
+          for (int j = 0; j < 4; ++j) sgd_update(params, lrate, gsc, frag, pj[j], w0[j], v[j]);
+        }
+      } else if (hp) {
+        const optdev::Hyper h = optdev::load_hyper<OPT - 1>(hp, *s_stepw);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) opt_update(h, pj[j], w0[j], m0[j], v0[j], v[j]);
       }
     }
   } else {
@@ -1574,7 +1628,9 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
       b1st[c] = *reinterpret_cast<const u16x8*>(brow + kc);
     }
     load_scalars();
+    load_step();
     float w0[4] = {0.f, 0.f, 0.f, 0.f}, g0[4] = {0.f, 0.f, 0.f, 0.f};  // wave 0's outputs (j0 + 4 lg + r, i0 + lr)
+    float m0[4] = {0.f, 0.f, 0.f, 0.f}, v0[4] = {0.f, 0.f, 0.f, 0.f};  // their optimiser state (OPT != 0)
     if (wid == 0 && act) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -1583,6 +1639,12 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
           const int p = O_FC1W + j * NIN + i0 + lr;
           if (hp) w0[r] = params[p];
           if (accumulate) g0[r] = grads[p];
+          if constexpr (OPT != 0) {
+            if (hp) m0[r] = om[p];
+          }
+          if constexpr (OPT >= 2) {
+            if (hp) v0[r] = ov[p];
+          }
         }
       }
     }
@@ -1616,6 +1678,7 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
     }
     f32x4* wpart = part;
     if (act) wpart[wid * 64 + lane] = acc0 + acc1;
+    park_step();
     __syncthreads();
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
     const int i = i0 + lr;
@@ -1654,6 +1717,10 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
       xgmi_finish(xv, rb, epoch);
     }
     if (wid == 0 && ok) {
+      optdev::Hyper h{};
+      if constexpr (OPT != 0) {
+        if (hp) h = optdev::load_hyper<OPT - 1>(hp, *s_stepw);
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int j = j0 + lg * 4 + r;
@@ -1662,7 +1729,11 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
           float g = v[r];
           if (accumulate) g += g0[r];
           grads[p] = g;
-          if (hp) sgd_update(params, lrate, gsc, frag, p, w0[r], g);
+          if constexpr (OPT == 0) {
+            if (hp) sgd_update(params, lrate, gsc, frag, p, w0[r], g);
+          } else if (hp) {
+            opt_update(h, p, w0[r], m0[r], v0[r], g);
+          }
         }
       }
     }
@@ -1675,11 +1746,34 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
     if (lane == 0) {
       loss[0] = s / static_cast<float>(B);
       rng[0] += 1;  // advance the dropout stream for the next step
-      if (hp != nullptr && step != nullptr) step[0] += 1;  // the fused SGD's device step counter
+      if constexpr (OPT == 0) {
+        if (hp != nullptr && step != nullptr) step[0] += 1;  // the fused SGD's device step counter
+      }
+    }
+  }
+  if constexpr (OPT != 0) {
+    // every block read the old count before its arrival (a block whose exchange failed arrives too, or the
+    // ticket would never clear); the last one publishes.  The next launch sees the stores across the kernel
+    // boundary: a relaxed device-scope ticket is enough (optim_device.h run_chunks)
+    __syncthreads();
+    if (tid == 0) {
+      const int prev = atomicAdd(step + 1, 1);
+      if (prev == static_cast<int>(gridDim.x) - 1) {
+        step[0] = step0 + 1;
+        step[1] = 0;
+      }
     }
   }
 }
 
+template <class A>
+__device__ __forceinline__ void arg_live(A a) {
+  asm volatile("" ::"s"(a));
+}
+
+// State: nothing for OPT 0 (plain SGD's kernel keeps exactly its arguments), else the two flat state pointers
+// (float* om, float* ov) of cnn_reduce_role's stateful modes.
+template <int OPT, class... State>
 __global__ __launch_bounds__(RED_T) void k_cnn_reduce(const float* __restrict__ slabs, int nwg,
                                                       const uint16_t* __restrict__ acts,
                                                       const float* __restrict__ gscale, float* __restrict__ grads,
@@ -1687,15 +1781,17 @@ __global__ __launch_bounds__(RED_T) void k_cnn_reduce(const float* __restrict__ 
                                                       float* __restrict__ loss, unsigned long long* __restrict__ rng,
                                                       float* __restrict__ params, const float* __restrict__ hp,
                                                       uint16_t* __restrict__ frag, int* __restrict__ step,
-                                                      XgmiView xv, float xscale, int rb0) {
+                                                      XgmiView xv, float xscale, int rb0, State... state) {
+  static_assert(sizeof...(State) == (OPT != 0 ? 2 : 0), "the stateful modes take om and ov");
   __shared__ f32x4 part[RED_LANES * RED_COLS];  // slab: [lane][column]; fc1: [wave][lane] (same 8 KB)
   __shared__ uint32_t s_epoch;
   __shared__ int s_fail;
   // every argument live here: the kernel-argument segment arrives behind one wait, ahead of the first request
   asm volatile("" ::"s"(slabs), "s"(nwg), "s"(acts), "s"(gscale), "s"(grads), "s"(accumulate), "s"(loss_part), "s"(B),
                "s"(loss), "s"(rng), "s"(params), "s"(hp), "s"(frag), "s"(step), "s"(xv.size), "s"(xscale), "s"(rb0));
-  cnn_reduce_role(rb0 + blockIdx.x, part, &s_epoch, &s_fail, slabs, nwg, acts, gscale, grads, accumulate, loss_part, B,
-                  loss, rng, params, hp, frag, step, xv, xscale);
+  (arg_live(state), ...);
+  cnn_reduce_role<OPT>(rb0 + blockIdx.x, part, &s_epoch, &s_fail, slabs, nwg, acts, gscale, grads, accumulate,
+                       loss_part, B, loss, rng, params, hp, frag, step, xv, xscale, state...);
 }
 
 __device__ void cnn_fused_tail(const CnnTail& tl, int rb, f32x4* part, uint32_t* s_epoch, int* s_fail,
@@ -1703,8 +1799,8 @@ __device__ void cnn_fused_tail(const CnnTail& tl, int rb, f32x4* part, uint32_t*
   if (rb >= RED_BLOCKS) return;  // block-uniform: workgroups past the roles are done
   XgmiView one{};
   one.size = 1;
-  cnn_reduce_role(rb, part, s_epoch, s_fail, slabs, nwg, acts, tl.gscale, tl.grads, tl.accumulate, loss_part, tl.B,
-                  tl.loss, tl.rng, tl.params, tl.hp, tl.frag, tl.step, one, 1.f);
+  cnn_reduce_role<0>(rb, part, s_epoch, s_fail, slabs, nwg, acts, tl.gscale, tl.grads, tl.accumulate, loss_part,
+                     tl.B, tl.loss, tl.rng, tl.params, tl.hp, tl.frag, tl.step, one, 1.f);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1912,8 +2008,13 @@ hipError_t cnn_train_fused(const float* images, const int64_t* tgt, int B, float
                            float* loss_part, uint16_t* acts, int nwg, float* loss, float* grads, const float* gscale,
                            int accumulate, hipStream_t s, unsigned long long* stamps, int prep,
                            const float* sgd_hp, int stop_after, int* sgd_step, const XgmiView* xv,
-                           float xscale) {
+                           float xscale, int opt_mode, float* opt_m, float* opt_v) {
   if (reinterpret_cast<uintptr_t>(grads) & 15) return hipErrorInvalidValue;  // float4 gradient stores
+  // a stateful update (cnn_reduce_role's OPT) needs its hyper-parameters, the step words and its state
+  if (opt_mode < 0 || opt_mode > 3) return hipErrorInvalidValue;
+  if (opt_mode != 0 && (sgd_hp == nullptr || sgd_step == nullptr || opt_m == nullptr ||
+                        (opt_mode >= 2 && opt_v == nullptr)))
+    return hipErrorInvalidValue;
   XgmiView view{};
   view.size = 1;
   if (xv != nullptr && xv->size > 1) {
@@ -1953,7 +2054,9 @@ hipError_t cnn_train_fused(const float* images, const int64_t* tgt, int B, float
   CnnTail tail{};
   unsigned* bar = nullptr;
   int* berr = nullptr;
-  if (view.size == 1 && stamps == nullptr && stop_after < 0 && cnn_fused_tail_enabled() && nwg >= RED_BLOCKS &&
+  // (the stateful updates always take the two-launch form: the tail is instantiated for plain SGD only)
+  if (opt_mode == 0 && view.size == 1 && stamps == nullptr && stop_after < 0 && cnn_fused_tail_enabled() &&
+      nwg >= RED_BLOCKS &&
       nwg <= cnn_device_cus() && cnn_barrier_words(s, &bar, &berr)) {
     tail.gscale = gscale; tail.grads = grads; tail.loss = loss; tail.rng = rng; tail.params = params;
     tail.hp = sgd_hp; tail.frag = static_cast<uint16_t*>(frag); tail.step = sgd_step; tail.bar = bar;
@@ -1969,9 +2072,19 @@ hipError_t cnn_train_fused(const float* images, const int64_t* tgt, int B, float
   if (!tail.on && !(diag & 1)) {
     const int rb0 = (diag & 8) ? RED_SLAB_BLOCKS : 0;
     const int nrb = (diag & 4) ? RED_SLAB_BLOCKS : (diag & 8) ? RED_BLOCKS - RED_SLAB_BLOCKS : RED_BLOCKS;
-    hipLaunchKernelGGL(k_cnn_reduce, dim3(nrb), dim3(RED_T), 0, s, slabs, nwg, acts, gscale, grads,
-                       accumulate, loss_part, B, loss, rng, params, (diag & 16) ? nullptr : sgd_hp,
-                       static_cast<uint16_t*>(frag), sgd_step, view, xscale, rb0);
+    const float* hp = (diag & 16) ? nullptr : sgd_hp;
+    uint16_t* fr = static_cast<uint16_t*>(frag);
+    if (opt_mode == 0) {
+      hipLaunchKernelGGL(k_cnn_reduce<0>, dim3(nrb), dim3(RED_T), 0, s, slabs, nwg, acts, gscale, grads,
+                         accumulate, loss_part, B, loss, rng, params, hp, fr, sgd_step, view, xscale, rb0);
+    } else {
+      using ReduceFn = decltype(&k_cnn_reduce<1, float*, float*>);
+      static const ReduceFn kReduce[3] = {&k_cnn_reduce<1, float*, float*>, &k_cnn_reduce<2, float*, float*>,
+                                          &k_cnn_reduce<3, float*, float*>};
+      hipLaunchKernelGGL(kReduce[opt_mode - 1], dim3(nrb), dim3(RED_T), 0, s, slabs, nwg, acts, gscale, grads,
+                         accumulate, loss_part, B, loss, rng, params, hp, fr, sgd_step, view, xscale, rb0, opt_m,
+                         opt_v);
+    }
   }
   return hipGetLastError();
 }
@@ -2009,6 +2122,11 @@ hipError_t cnn_sgd_fused(float* params, const float* grads, const float* hp, voi
 // multi-tensor update launch and the next step's fragment prep launch become ONE launch.  hp / step: the fused
 // optimiser's device hyper-parameters and {steps taken, arrival counter}, read and advanced exactly as its own
 // update kernel does (optim_device.h run_chunks), so its state_dict and later steps stay consistent.
+//
+// MODE: optdev's (0 SGD with momentum and / or L2 weight decay -- m: the momentum buffers, v unused; 1 Adam with
+// L2; 2 AdamW).  The stateful updates after an all-reduce that did not run inside the slab reduction (RCCL, the
+// fusion engine, DDP); plain SGD keeps k_cnn_sgd.
+template <int MODE>
 __global__ __launch_bounds__(256) void k_cnn_adamw(float* __restrict__ params, const float* __restrict__ grads,
                                                    float* __restrict__ m, float* __restrict__ v,
                                                    const float* __restrict__ hp, int* __restrict__ step,
@@ -2016,14 +2134,15 @@ __global__ __launch_bounds__(256) void k_cnn_adamw(float* __restrict__ params, c
   __shared__ int s_step;
   if (threadIdx.x == 0) s_step = step[0] + 1;
   __syncthreads();
-  const optdev::Hyper h = optdev::load_hyper<2>(hp, s_step);
+  const optdev::Hyper h = optdev::load_hyper<MODE>(hp, s_step);
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p < NPARAM) {
-    float w = params[p], mm = m[p], vv = v[p];
-    optdev::update<2>(h, w, grads[p], mm, vv);
+    float w = params[p], mm = m[p], vv = 0.f;
+    if constexpr (MODE != 0) vv = v[p];
+    optdev::update<MODE>(h, w, grads[p], mm, vv);
     params[p] = w;
     m[p] = mm;
-    v[p] = vv;
+    if constexpr (MODE != 0) v[p] = vv;
     write_frag(frag, p, w);
   }
   __syncthreads();  // (every block read the old count before its arrival: the last one publishes)
@@ -2036,11 +2155,21 @@ __global__ __launch_bounds__(256) void k_cnn_adamw(float* __restrict__ params, c
   }
 }
 
-hipError_t cnn_adamw_fused(float* params, const float* grads, float* m, float* v, const float* hp, void* frag,
-                           int* step, hipStream_t s) {
-  hipLaunchKernelGGL(k_cnn_adamw, dim3(ceil_div(NPARAM, 256)), dim3(256), 0, s, params, grads, m, v, hp, step,
+// mode: optdev's MODE (0 SGD with momentum / weight decay, 1 Adam, 2 AdamW); v may be nullptr for mode 0
+hipError_t cnn_opt_fused(float* params, const float* grads, float* m, float* v, const float* hp, void* frag,
+                         int* step, int mode, hipStream_t s) {
+  if (mode < 0 || mode > 2 || m == nullptr || step == nullptr || (mode != 0 && v == nullptr))
+    return hipErrorInvalidValue;
+  using OptFn = decltype(&k_cnn_adamw<2>);
+  static const OptFn kOpt[3] = {&k_cnn_adamw<0>, &k_cnn_adamw<1>, &k_cnn_adamw<2>};
+  hipLaunchKernelGGL(kOpt[mode], dim3(ceil_div(NPARAM, 256)), dim3(256), 0, s, params, grads, m, v, hp, step,
                      static_cast<uint16_t*>(frag));
   return hipGetLastError();
+}
+
+hipError_t cnn_adamw_fused(float* params, const float* grads, float* m, float* v, const float* hp, void* frag,
+                           int* step, hipStream_t s) {
+  return cnn_opt_fused(params, grads, m, v, hp, frag, step, 2, s);
 }
 
 }  // namespace pde

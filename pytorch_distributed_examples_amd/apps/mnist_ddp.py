@@ -51,14 +51,17 @@ from ..utils import config as rtconfig
 from ..utils.config import add_runtime_args
 
 
-def load_train_objs(model_name: str, device, train_size: int, test_size: int, data_dir=None):
+def load_train_objs(model_name: str, device, train_size: int, test_size: int, data_dir=None,
+                    momentum: float = 0.0, weight_decay: float = 0.0):
     train_set, test_set = mnist_datasets(device, train_size, test_size, data_dir)
     if model_name == "cnn":
         from ..models.cnn import Net
 
         model = Net()
         loss = OF.nll_loss
-        make_opt = lambda params: FusedSGD(params, lr=0.01)  # noqa: E731  (mnist_horovod.py:50)
+        # (mnist_horovod.py:50 is plain SGD; --momentum / --weight_decay: the fused step applies those too)
+        make_opt = lambda params: FusedSGD(params, lr=0.01, momentum=momentum,  # noqa: E731
+                                           weight_decay=weight_decay)
     else:
         from ..models.mlp import reference_mlp
 
@@ -183,7 +186,7 @@ class Trainer:
 
     def _fused_cnn_step(self, source, targets):
         xgmi = getattr(self.ddp.comm, "xgmi", None)
-        if self.ddp.world == 1:  # SGD + fragment refresh inside the slab reduction
+        if self.ddp.world == 1:  # SGD (+ momentum / weight decay) + fragment refresh inside the slab reduction
             return self.fused.forward_backward(source, targets, grad_out=self.ddp.flat_grad, sgd=self.optimizer)
         if xgmi is not None:  # + the gradient all-reduce, exchanged over xGMI inside that kernel
             return self.fused.forward_backward(source, targets, grad_out=self.ddp.flat_grad, sgd=self.optimizer,
@@ -287,12 +290,15 @@ class Trainer:
         self.model.train(was)
 
 
-def main(argv=None):
+def build_parser():
     parser = argparse.ArgumentParser(description="simple distributed training job")
     parser.add_argument("total_epochs", type=int, help="Total epochs to train the model")
     parser.add_argument("save_every", type=int, help="How often to save a snapshot")
     parser.add_argument("--batch_size", default=128, type=int, help="Input batch size on each device (default: 128)")
     parser.add_argument("--model", default="mlp", choices=["mlp", "cnn"])
+    parser.add_argument("--momentum", type=float, default=0.0, help="--model cnn: SGD momentum (default: 0)")
+    parser.add_argument("--weight_decay", type=float, default=0.0,
+                        help="--model cnn: SGD L2 weight decay (default: 0)")
     parser.add_argument("--fused", action="store_true",
                         help="cnn: whole-network fused training kernel (GPU; the default GPU path, kept for scripts)")
     parser.add_argument("--layers", action="store_true",
@@ -311,7 +317,11 @@ def main(argv=None):
                              "python -m pytorch_distributed_examples_amd.launch.hvdrun")
     parser.add_argument("--commit_every", type=int, default=10, help="--rewire: steps between in-memory commits")
     add_runtime_args(parser, style="underscore")
-    args = parser.parse_args(argv)
+    return parser
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     cfg = rtconfig.apply(rtconfig.from_args(args))
     args.device = rtconfig.device_for(cfg, args.device)
 
@@ -331,7 +341,8 @@ def main(argv=None):
         log = RankLogger(ctx.rank)
         metrics = MetricsWriter(args.metrics) if args.metrics and ctx.rank == 0 else None
         train_set, test_set, model, make_opt, criterion = load_train_objs(args.model, ctx.device, args.train_size,
-                                                                          args.test_size, args.data_dir)
+                                                                          args.test_size, args.data_dir,
+                                                                          args.momentum, args.weight_decay)
         train_data = ShardedLoader(train_set, args.batch_size, ctx.world_size, ctx.rank, shuffle=True)
         test_data = ShardedLoader(test_set, args.batch_size, ctx.world_size, ctx.rank, shuffle=False)
         trainer = Trainer(ctx, model, train_data, test_data, make_opt, criterion, args.save_every,

@@ -35,11 +35,13 @@ from ..utils import config as rtconfig
 from ..utils.config import add_runtime_args
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="Horovod-style MNIST CNN")
     ap.add_argument("--epochs", type=int, default=50)
     ap.add_argument("--batch-size", type=int, default=1024)
     ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--momentum", type=float, default=0.0, help="SGD momentum (default: 0, the reference)")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="SGD L2 weight decay (default: 0)")
     ap.add_argument("--train-size", type=int, default=60000)
     ap.add_argument("--data-dir", default=None,
                     help="directory with the four MNIST IDX files (plain or .gz; also DIR/MNIST/raw, DIR/raw); never "
@@ -51,7 +53,11 @@ def main(argv=None):
     ap.add_argument("--graph-chunk", type=int, default=50, help="GPU: training steps per hipGraph replay")
     ap.add_argument("--compression", default="none", choices=["none", "fp16", "bf16"])
     add_runtime_args(ap)
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     _cfg = rtconfig.apply(rtconfig.from_args(args))
     if hasattr(args, "device"):
         args.device = rtconfig.device_for(_cfg, args.device)
@@ -63,7 +69,7 @@ def main(argv=None):
 
     model = Net().to(dev)
     fast = dev.type == "cuda" and not args.layers
-    optimizer = FusedSGD(model.parameters(), lr=args.lr)
+    optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
     optimizer = hvd.DistributedOptimizer(optimizer, named_parameters=model.named_parameters(),
                                          compression=getattr(hvd.Compression, "bf16" if args.compression == "none"
                                                              and _cfg.grad_dtype == "bf16" else args.compression))

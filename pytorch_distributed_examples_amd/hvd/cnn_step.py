@@ -27,18 +27,19 @@ class FusedHvdStep:
     def __init__(self, model, optimizer, batch: int, graph: bool = True):
         self.model, self.opt, self.batch = model, optimizer, int(batch)
         self.fused = FusedCNN(model)
+        from ..models.cnn_fused import fused_update_mode, opt_in_reduce_enabled
         from ..ops.optim import FusedSGD
 
-        # plain FusedSGD (the DP script, mnist_horovod.py:50): the update rides in the fused kernel's slab reduction
-        # at world 1, else ONE launch after the engine's synchronize that also refreshes the bf16 fragment image --
-        # the bench's hvd_cnn step.  Other optimisers (AdamW): the multi-tensor update, fragments rebuilt in-kernel.
-        from ..ops.optim import FusedAdamW
-
-        g = optimizer.param_groups[0] if len(optimizer.param_groups) == 1 else None
-        self.sgd_fast = (isinstance(optimizer, FusedSGD) and g is not None and g.get("momentum", 0.0) == 0.0
-                         and g.get("weight_decay", 0.0) == 0.0)
-        # one-group FusedAdamW (the elastic script): update + fragment refresh in ONE launch (FusedCNN.adamw_step)
-        self.adamw_fast = isinstance(optimizer, FusedAdamW) and g is not None
+        # a one-group FusedSGD (the DP script, mnist_horovod.py:50; any momentum / weight decay): the update rides in
+        # the fused kernel's slab reduction at world 1, else ONE launch after the engine's synchronize that also
+        # refreshes the bf16 fragment image -- the bench's hvd_cnn step.  A one-group FusedAdamW (the elastic script)
+        # or FusedAdam: update + fragment refresh in ONE launch (FusedCNN.opt_step); at world 1 inside the slab
+        # reduction too (PDE_CNN_OPT_IN_REDUCE=0 keeps the launch of its own).  Anything else: the wrapped
+        # optimiser's own step, fragments rebuilt in-kernel.
+        self.mode = fused_update_mode(optimizer)
+        self.sgd_fast = self.mode is not None and isinstance(optimizer, FusedSGD)
+        self.adamw_fast = self.mode is not None and not self.sgd_fast
+        self.adam_in_reduce = self.adamw_fast and opt_in_reduce_enabled()
         self.fused.always_prep = not (self.sgd_fast or self.adamw_fast)
         if not self.sgd_fast:
             from ..ops import functional as OF
@@ -66,11 +67,17 @@ class FusedHvdStep:
             with self.opt.skip_synchronize():
                 self.fused.sgd_step(self.opt, self.grads)
             return loss
+        if self.adam_in_reduce:
+            from . import core
+
+            if core.size() == 1:  # all-reduce = identity: Adam / AdamW inside the reduction kernel
+                self.opt.synchronize()
+                return self.fused.forward_backward(x, y, grad_out=self.grads, opt=self.opt)
         loss = self.fused.forward_backward(x, y, grad_out=self.grads)
         if self.adamw_fast:
             self.opt.synchronize()  # the engine (graph mode: stream-ordered on this stream)
             with self.opt.skip_synchronize():
-                self.fused.adamw_step(self.opt, self.grads)
+                self.fused.opt_step(self.opt, self.grads)
             return loss
         self.opt.step()
         return loss

@@ -14,21 +14,26 @@ straight into a flat gradient buffer -- the DDP wrapper's, when it is laid out i
 Semantics match ``nll_loss(net(x), y)`` + ``backward()`` in train mode, including Dropout2d(p=0.5) on
 conv2's output and dropout(p=0.5) on fc1's (fresh masks every call; dropout disabled in eval mode).
 
-Fused optimiser step (plain SGD, the reference's ``optim.SGD(lr=0.01)``, mnist_horovod.py:50): the training
-kernel reads the conv weights as a bf16 MFMA fragment image that a prep kernel writes from the fp32
-parameters.  With ``sgd=opt`` (single process) the slab reduction also applies the SGD update and rewrites
-the fragment slots of the weights it updates; with :meth:`sgd_step` (after the gradient all-reduce) one
-kernel does the same.  Either way the next step skips the prep launch::
+Fused optimiser step: the training kernel reads the conv weights as a bf16 MFMA fragment image that a prep
+kernel writes from the fp32 parameters.  With ``sgd=opt`` (or ``opt=opt``) the slab reduction also applies the
+optimiser update and rewrites the fragment slots of the weights it updates; with :meth:`opt_step`
+(:meth:`sgd_step` / :meth:`adam_step` / :meth:`adamw_step`, after the gradient all-reduce) one kernel does the
+same.  Either way the next step skips the prep launch.  ``opt`` is a one-group ``FusedSGD`` (plain -- the
+reference's ``optim.SGD(lr=0.01)``, mnist_horovod.py:50 -- or with momentum and / or weight decay),
+``FusedAdam`` or ``FusedAdamW`` (:func:`fused_update_mode`); the stateful ones keep ``momentum_buffer`` /
+``exp_avg`` / ``exp_avg_sq`` as views of flat buffers, so ``state_dict()`` and ``opt.step()`` see the same state::
 
+    opt = FusedSGD(net.parameters(), lr=0.01, momentum=0.9, weight_decay=1e-4)
     loss = fused.forward_backward(x, y, grad_out=buf, sgd=opt)          # world 1: 2 launches per step
     loss = fused.forward_backward(x, y, grad_out=g, sgd=opt, xgmi=xa)   # world > 1 on one node: 2 launches
     loss = fused.forward_backward(x, y, grad_out=ddp.flat_grad)         # world > 1, any data plane:
     ddp.sync_gradients(); fused.sgd_step(opt, ddp.flat_grad)            #   3 launches + all-reduce
+    loss = fused.forward_backward(x, y, opt=adamw)                      # a FusedAdamW: AdamW in the reduction
 
 With ``xgmi`` (a :class:`..parallel.xgmi_allreduce.XgmiAllreduce` over the data-parallel ranks) the slab
 reduction exchanges every workgroup's gradient chunk with all peers over xGMI inside the same kernel and
 sums the ranks' chunks in rank order (``avg``: x 1/world), so ``grad_out`` receives the all-reduced
-gradients, identical on every rank, and the SGD update stays fused -- the all-reduce costs no launch.
+gradients, identical on every rank, and the update stays fused -- the all-reduce costs no launch.
 
 The fragment image is re-derived (prep launch) whenever anything other than these fused updates may have
 written the weights: any other optimiser step bumps the weight generation (:func:`.functional.
@@ -84,44 +89,25 @@ class FusedCNN:
         """The fp32 weights were written behind our back: rebuild the fragment image next step."""
         self._frag_gen = None
 
-    @staticmethod
-    def _sgd_hp(opt):
-        """Device hyper-parameters of a FusedSGD that the fused update can apply (plain SGD only)."""
-        from ..ops.optim import FusedSGD
-
-        assert isinstance(opt, FusedSGD) and len(opt.param_groups) == 1, "fused update needs one FusedSGD group"
-        group = opt.param_groups[0]
-        assert group["momentum"] == 0.0 and group["weight_decay"] == 0.0, "fused update is plain SGD"
-        params = [p for p in group["params"] if p.grad is not None]
-        st = opt._group_dev(0, group, params)
-        for p in params:  # the fused update writes the fp32 weights only (plus its own fragment image)
-            OF.release_compute_copies(p)
-        return (st["hp"], st["step"]), params
-
-    def _after_update(self, opt, params):
-        # the step count lives in the optimizer's device counter (advanced by the fused kernels, so hipGraph
-        # replays count too); FusedSGD.state_dict() reads it back
-        OF.bump_weight_generation()
-        self._frag_gen = OF.weight_generation()
-
-    @torch.no_grad()
-    def sgd_step(self, opt, grads: torch.Tensor):
-        """``opt.step()`` for the flat parameters (plain SGD) fused with the fragment-image refresh."""
-        (hp, step), params = self._sgd_hp(opt)
-        _native.C().cnn_sgd(self.flat, grads, hp, self.frag, step)
-        self._after_update(opt, params)
-
-    def _bind_adamw_state(self, opt):
-        """The FusedAdamW's exp_avg / exp_avg_sq become views of two flat buffers (state_dict keeps working); a state
-        tensor replaced behind our back (load_state_dict of an elastic restore) is copied in and re-bound."""
-        if getattr(self, "_adam_m", None) is None:
-            self._adam_m = torch.zeros_like(self.flat)
-            self._adam_v = torch.zeros_like(self.flat)
+    def _bind_state(self, opt, mode: int):
+        """The optimiser's per-parameter state -- ``momentum_buffer`` (SGD with momentum) or ``exp_avg`` /
+        ``exp_avg_sq`` (Adam, AdamW) -- becomes views of two flat buffers indexed like ``self.flat`` (state_dict keeps
+        working, and the multi-tensor ``opt.step()`` and the fused updates share one state); a state tensor replaced
+        behind our back (``load_state_dict``, an elastic restore) is copied in and re-bound."""
+        if mode == 0:
+            return
+        if getattr(self, "_opt_m", None) is None:
+            self._opt_m = torch.zeros_like(self.flat)
+            self._opt_v = torch.zeros_like(self.flat)
+        if mode == 1:
+            keys = (("momentum_buffer", self._opt_m),) if opt.param_groups[0]["momentum"] != 0.0 else ()
+        else:
+            keys = (("exp_avg", self._opt_m), ("exp_avg_sq", self._opt_v))
         off = 0
         for p in self.params:
             k = p.numel()
             st = opt.state[p]
-            for key, flat in (("exp_avg", self._adam_m), ("exp_avg_sq", self._adam_v)):
+            for key, flat in keys:
                 view = flat[off:off + k].view_as(p)
                 cur = st.get(key)
                 if cur is None or cur.data_ptr() != view.data_ptr():
@@ -133,21 +119,64 @@ class FusedCNN:
                     st[key] = view
             off += k
 
-    @torch.no_grad()
-    def adamw_step(self, opt, grads: torch.Tensor):
-        """``opt.step()`` of a one-group FusedAdamW over the flat parameters fused with the fragment-image refresh:
-        ONE launch (``k_cnn_adamw``) instead of the multi-tensor update plus the next step's prep launch; the update
-        math and the device step counter are the optimiser's own (optim_device.h)."""
-        from ..ops.optim import FusedAdamW
-
-        assert isinstance(opt, FusedAdamW) and len(opt.param_groups) == 1, "adamw_step needs one FusedAdamW group"
-        self._bind_adamw_state(opt)
+    def _update_args(self, opt):
+        """``(mode, device state, params)`` of an optimiser the fused update can apply (:func:`fused_update_mode`):
+        its state bound to the flat buffers BEFORE the optimiser builds its device table, so both see one state."""
+        mode = fused_update_mode(opt)
+        assert mode is not None, "fused update needs a one-group FusedSGD, FusedAdam or FusedAdamW"
+        self._bind_state(opt, mode)
         group = opt.param_groups[0]
         params = [p for p in group["params"] if p.grad is not None]
         st = opt._group_dev(0, group, params)
-        _native.C().cnn_adamw(self.flat, grads, self._adam_m, self._adam_v, st["hp"], self.frag, st["step"])
+        for p in params:  # the fused update writes the fp32 weights only (plus its own fragment image)
+            OF.release_compute_copies(p)
+        return mode, st, params
+
+    def _after_update(self, opt, params):
+        # the step count lives in the optimizer's device counter (advanced by the fused kernels, so hipGraph
+        # replays count too); the optimiser's state_dict() reads it back
         OF.bump_weight_generation()
         self._frag_gen = OF.weight_generation()
+
+    @torch.no_grad()
+    def opt_step(self, opt, grads: torch.Tensor):
+        """``opt.step()`` for the flat parameters fused with the fragment-image refresh, ONE launch: plain SGD
+        (``k_cnn_sgd``), SGD with momentum / weight decay, Adam or AdamW (``k_cnn_adamw<MODE>``) -- the update after
+        a gradient all-reduce that ran outside the reduction kernel.  The update math and the device step counter are
+        the optimiser's own (optim_device.h)."""
+        mode, st, params = self._update_args(opt)
+        C = _native.C()
+        if mode == 0:
+            C.cnn_sgd(self.flat, grads, st["hp"], self.frag, st["step"])
+        else:
+            C.cnn_opt(self.flat, grads, self._opt_m, self._opt_v if mode >= 2 else None, st["hp"], self.frag,
+                      st["step"], mode - 1)
+        self._after_update(opt, params)
+
+    def sgd_step(self, opt, grads: torch.Tensor):
+        """:meth:`opt_step` of a one-group FusedSGD (any momentum / weight decay)."""
+        from ..ops.optim import FusedSGD
+
+        assert isinstance(opt, FusedSGD), "sgd_step needs a FusedSGD"
+        self.opt_step(opt, grads)
+
+    def adam_step(self, opt, grads: torch.Tensor):
+        """:meth:`opt_step` of a one-group FusedAdam (L2 weight decay)."""
+        from ..ops.optim import FusedAdam
+
+        assert isinstance(opt, FusedAdam), "adam_step needs a FusedAdam"
+        self.opt_step(opt, grads)
+
+    @torch.no_grad()
+    def adamw_step(self, opt, grads: torch.Tensor):
+        """``opt.step()`` of a one-group FusedAdamW over the flat parameters fused with the fragment-image refresh:
+        ONE launch (``k_cnn_adamw``) instead of the multi-tensor update plus the next step's prep launch."""
+        from ..ops.optim import FusedAdamW
+
+        assert isinstance(opt, FusedAdamW) and len(opt.param_groups) == 1, "adamw_step needs one FusedAdamW group"
+        _, st, params = self._update_args(opt)
+        _native.C().cnn_adamw(self.flat, grads, self._opt_m, self._opt_v, st["hp"], self.frag, st["step"])
+        self._after_update(opt, params)
 
     def _nwg(self, B: int) -> int:
         if self.workgroups:
@@ -168,27 +197,37 @@ class FusedCNN:
 
     def forward_backward(self, x: torch.Tensor, y: torch.Tensor, grad_out: torch.Tensor | None = None,
                          accumulate: bool = False, p_drop2: float = 0.5, p_drop1: float = 0.5,
-                         sgd=None, xgmi=None, avg: bool = True) -> torch.Tensor:
+                         sgd=None, xgmi=None, avg: bool = True, opt=None) -> torch.Tensor:
         """Loss (device scalar) of the local batch; gradients of the mean loss written to ``grad_out``.
 
-        ``sgd``: a plain FusedSGD over these parameters -- also take the optimiser step.
+        ``sgd`` / ``opt`` (synonyms; pass one): a one-group FusedSGD (any momentum / weight decay), FusedAdam or
+        FusedAdamW over these parameters -- also take the optimiser step, inside the reduction kernel.
         ``xgmi``: an XgmiAllreduce over the data-parallel ranks -- ``grad_out`` receives the all-reduced
         gradients (``avg``: averaged), exchanged inside the reduction kernel."""
         C = _native.C()
+        if sgd is not None and opt is not None:
+            raise ValueError("forward_backward: pass the optimiser as sgd= or opt=, not both")
+        opt = sgd if opt is None else opt
         if grad_out is None:
             grad_out = self.grad_buffer()
         x = x.float().contiguous()
         y = y.long().contiguous()
         training = self.net.training
         prep = self.always_prep or self._frag_gen is None or self._frag_gen != OF.weight_generation()
-        (hp, step), params = self._sgd_hp(sgd) if sgd is not None else ((None, None), None)
+        mode, hp, step, params, om, ov = 0, None, None, None, None, None
+        if opt is not None:
+            mode, st, params = self._update_args(opt)
+            hp, step = st["hp"], st["step"]
+            if mode != 0:
+                om, ov = self._opt_m, (self._opt_v if mode >= 2 else None)
         view, xscale = None, 1.0
         if xgmi is not None and xgmi.size > 1:
             view, xscale = xgmi.view(), (1.0 / xgmi.size if avg else 1.0)
         loss = C.cnn_train(x, y, self.flat, OF._rng_counter(x.device), p_drop2, p_drop1, training, grad_out,
-                           accumulate, None, self.stamps, self.frag, prep, hp, self.stop_after, step, view, xscale)
-        if sgd is not None:
-            self._after_update(sgd, params)
+                           accumulate, None, self.stamps, self.frag, prep, hp, self.stop_after, step, view, xscale,
+                           mode, om, ov)
+        if opt is not None:
+            self._after_update(opt, params)
         else:
             # the weights did not change: the image stays current until someone writes them
             self._frag_gen = OF.weight_generation()
@@ -223,6 +262,26 @@ class FusedCNN:
             stats = CnnEvalStats(self.flat.device)
         _, logp = self._eval(x, y, stats, False, logprobs)
         return (stats, logp) if logprobs else stats
+
+
+def fused_update_mode(opt) -> int | None:
+    """The update mode of the fused CNN kernels for ``opt``: 0 plain SGD, 1 SGD with momentum and / or L2 weight
+    decay, 2 Adam (L2), 3 AdamW -- for a one-group FusedSGD / FusedAdam / FusedAdamW (a ``hvd.DistributedOptimizer``
+    around one too); ``None`` for anything else, which keeps ``opt.step()``.  Pure: needs no native module."""
+    from ..ops.optim import FusedAdam, FusedAdamW, FusedSGD
+
+    if not isinstance(opt, (FusedSGD, FusedAdam, FusedAdamW)) or len(opt.param_groups) != 1:
+        return None
+    if isinstance(opt, FusedSGD):
+        group = opt.param_groups[0]
+        return 0 if group["momentum"] == 0.0 and group["weight_decay"] == 0.0 else 1
+    return 2 if isinstance(opt, FusedAdam) else 3
+
+
+def opt_in_reduce_enabled() -> bool:
+    """Single process, FusedAdam / FusedAdamW: take the update inside the reduction kernel (two launches per step)
+    instead of the one-launch update behind it (three); ``PDE_CNN_OPT_IN_REDUCE=0|1`` is the A/B switch."""
+    return os.environ.get("PDE_CNN_OPT_IN_REDUCE", "1") != "0"
 
 
 def fused_eval_enabled() -> bool:
