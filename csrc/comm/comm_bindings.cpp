@@ -3,6 +3,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPGuard.h>
 
+#include "adasum_weights.h"
 #include "comm_manager.h"
 #include "fusion_engine.h"
 #include "p2p_ring.h"
@@ -41,6 +42,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "MI355X communication runtime: RCCL communicator manager and tensor-fusion engine";
   m.def("rccl_unique_id", []() { return py::bytes(pde::rccl_unique_id()); });
   m.def("rccl_version", &pde::rccl_version);
+  // the Adasum tree's weights from the ranks' Gram matrix: the function the combine kernel runs (adasum_weights.h)
+  m.def("adasum_weights", [](const at::Tensor& gram) {
+    TORCH_CHECK(!gram.is_cuda() && gram.scalar_type() == at::kDouble && gram.dim() == 2 &&
+                    gram.size(0) == gram.size(1),
+                "adasum_weights: an [N, N] float64 CPU tensor");
+    const int n = static_cast<int>(gram.size(0));
+    TORCH_CHECK(n >= 1 && (n & (n - 1)) == 0, "adasum_weights: N must be a power of two");
+    const at::Tensor g = gram.contiguous();
+    at::Tensor w = at::empty({n}, g.options());
+    pde::adasum_weights(g.data_ptr<double>(), n, w.data_ptr<double>());
+    return w;
+  });
+  m.attr("ADASUM_EPS") = pde::kAdasumEps;
+  m.attr("MAX_ADASUM_SEGS") = pde::kMaxAdasumSegs;
 
   py::class_<RcclComm, std::shared_ptr<RcclComm>>(m, "RcclComm")
       .def(py::init<>())
@@ -157,6 +172,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return t;
            },
            py::arg("tensor"), py::arg("scale") = 1.0, py::arg("wire_bf16") = false)
+      // hvd.Adasum of the ranks' tensors, per segment (seg_lengths: element counts of the fused tensors); in place
+      // on the caller's CURRENT stream, two launches, hipGraph-capturable
+      .def("adasum_",
+           [](XgmiAllreduce& x, at::Tensor& t, const std::vector<int64_t>& seg_lengths, double scale) {
+             check_gpu(t);
+             TORCH_CHECK(t.scalar_type() == at::kFloat, "xgmi adasum: fp32 tensors");
+             x.adasum(t.data_ptr<float>(), t.data_ptr<float>(), t.numel(), seg_lengths, static_cast<float>(scale),
+                      cur(t));
+             return t;
+           },
+           py::arg("tensor"), py::arg("seg_lengths"), py::arg("scale") = 1.0)
       .def("view",
            [](const XgmiAllreduce& x) {  // flat device view for kernels that fold the exchange in (xgmi_view.h)
              const pde::XgmiView v = x.view();

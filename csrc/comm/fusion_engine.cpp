@@ -741,9 +741,12 @@ std::vector<Batch> FusionEngine::make_batches(std::vector<Request>& ready) {
       const bool same = h.tensor.device() == r.tensor.device() && h.tensor.scalar_type() == r.tensor.scalar_type() &&
                         h.op == r.op && h.prescale == r.prescale && h.postscale == r.postscale &&
                         h.compress == r.compress;
-      if (!same || open.bytes + bytes > fusion_bytes_.load() ||
-          static_cast<int>(open.reqs.size()) >= kMaxPackSegs * 8)
-        close();
+      // an Adasum batch is ONE xGMI call: it closes at the exchange's max_bytes and at its segment table's cap
+      const bool adasum_gpu = r.op == kOpAdasum && r.tensor.is_cuda() && xgmi_;
+      const int64_t limit = adasum_gpu ? std::min<int64_t>(fusion_bytes_.load(), xgmi_->max_bytes())
+                                       : fusion_bytes_.load();
+      const int max_reqs = adasum_gpu ? kMaxAdasumSegs : kMaxPackSegs * 8;
+      if (!same || open.bytes + bytes > limit || static_cast<int>(open.reqs.size()) >= max_reqs) close();
     }
     open.bytes += bytes;
     open.reqs.push_back(std::move(r));
@@ -865,13 +868,32 @@ void FusionEngine::run_allreduce_gpu(Batch& b, hipStream_t s, at::Tensor& stage,
   for (auto& r : b.reqs) total += r.tensor.numel();
   const bool span = adjacent_inplace(b);
   // one-shot xGMI exchange for latency-bound fp32 batches (Sum / Average; pre/post scale folded in)
-  if (xgmi_ && dt == 0 && (r0.op == 0 || r0.op == 1) && total * 4 <= xgmi_threshold_) {
+  // Adasum: the same span-or-pack route, the tensors as the call's segments (per-tensor dot products); it has no
+  // other data plane, so what the exchange cannot take is an error, never a sum
+  const bool adasum = r0.op == kOpAdasum;
+  std::vector<int64_t> segs;
+  if (adasum) {
+    TORCH_CHECK(xgmi_, "Adasum on GPU tensors needs the xGMI data plane (one node, PDE_HVD_DATA_PLANE=auto or xgmi); "
+                       "there is no RCCL form");
+    TORCH_CHECK(dt == 0, "Adasum on GPU tensors: fp32 only");
+    TORCH_CHECK(!r0.compress, "Adasum has no compressed (bf16) wire");
+    TORCH_CHECK(total * 4 <= xgmi_->max_bytes(), "Adasum: a tensor of ", total * 4,
+                " B exceeds the xGMI exchange's max_bytes (", xgmi_->max_bytes(), " B)");
+    for (auto& r : b.reqs)
+      if (r.tensor.numel() > 0) segs.push_back(r.tensor.numel());
+  }
+  if (adasum || (xgmi_ && dt == 0 && (r0.op == 0 || r0.op == 1) && total * 4 <= xgmi_threshold_)) {
     const float scale = static_cast<float>(r0.prescale * r0.postscale * (r0.op == 1 ? 1.0 / size_ : 1.0));
+    auto reduce = [&](float* p) {
+      if (adasum)
+        xgmi_->adasum(p, p, total, segs, scale, s);
+      else
+        xgmi_->allreduce(p, p, total, scale, s, r0.compress);
+    };
     ++n_xgmi_batches_;
     if (span) {
       ++n_inplace_batches_;
-      float* p = static_cast<float*>(r0.tensor.data_ptr());
-      xgmi_->allreduce(p, p, total, scale, s, r0.compress);
+      reduce(static_cast<float*>(r0.tensor.data_ptr()));
     } else {
       ensure_stage(stage, r0.tensor, total * 4, s, inline_mode);
       PackTable tab;
@@ -893,8 +915,7 @@ void FusionEngine::run_allreduce_gpu(Batch& b, hipStream_t s, at::Tensor& stage,
         (void)first;
         hip_ok(fusion_pack(tab, stage.data_ptr(), 0, 1.0f, s), "pack");
       }
-      float* f = static_cast<float*>(stage.data_ptr());
-      xgmi_->allreduce(f, f, total, scale, s, r0.compress);
+      reduce(static_cast<float*>(stage.data_ptr()));
       off = 0;
       i = 0;
       while (i < b.reqs.size()) {
@@ -1036,7 +1057,14 @@ void FusionEngine::run_allreduce_cpu(Batch& b) {
   at::Tensor fused = flats.size() == 1 ? flats[0].clone() : at::cat(flats);
   {
     py::gil_scoped_acquire g;
-    py_allreduce_(fused, r0.op);
+    if (r0.op == kOpAdasum) {  // per-tensor coefficients: the backend needs the tensors' extents in the buffer
+      TORCH_CHECK(!r0.compress, "Adasum has no compressed (bf16) wire");
+      std::vector<int64_t> segs;
+      for (auto& r : b.reqs) segs.push_back(r.tensor.numel());
+      py_allreduce_(fused, r0.op, segs);
+    } else {
+      py_allreduce_(fused, r0.op);
+    }
   }
   int64_t off = 0;
   for (auto& r : b.reqs) {

@@ -25,6 +25,9 @@
 //    xGMI peer all-reduce (every rank reads all peers' staged batch over its direct links: one kernel, no
 //    ring hops) when an XgmiAllreduce is attached; larger ones RCCL.  A batch whose tensors are adjacent views
 //    of one buffer (the flat gradient buffer of a fused model) is reduced in place, without pack / unpack.
+//    Adasum batches (op 10) take the same span-or-pack route into XgmiAllreduce::adasum with the tensors as its
+//    segments (per-tensor dot products); they close at the exchange's max_bytes and kMaxAdasumSegs tensors, and
+//    what the exchange cannot take (no xGMI plane, a larger tensor, a compressed wire) is an error, never a sum.
 //    Broadcast / allgather of GPU tensors without an RCCL communicator (several ranks rehearsing on one GPU)
 //    stage through the host over the CPU backend.
 //  * Graph mode (`allreduce_inline`): once the response cache holds a fixed tensor set, the optimizer may
@@ -65,6 +68,9 @@
 namespace pde {
 
 enum class ReqType { ALLREDUCE = 0, BROADCAST = 1, ALLGATHER = 2 };
+// hvd.Adasum (hvd/core.py ReduceOp.Adasum): per-tensor adaptive summation.  GPU: XgmiAllreduce::adasum on the fused
+// batch with the tensors as segments (no RCCL form, no bf16 wire); CPU: the Python backend gets the segment lengths.
+constexpr int kOpAdasum = 10;
 
 struct Request {
   int64_t handle = 0;
@@ -72,7 +78,7 @@ struct Request {
   std::string name;
   at::Tensor tensor;   // input
   at::Tensor output;   // output (== tensor for in-place)
-  int op = 1;          // 0 sum, 1 avg, 2 min, 3 max, 4 prod
+  int op = 1;          // 0 sum, 1 avg, 2 min, 3 max, 4 prod, 10 adasum
   int root = 0;
   double prescale = 1.0, postscale = 1.0;
   bool compress = false;  // fp32 -> bf16 on the wire

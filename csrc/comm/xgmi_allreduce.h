@@ -31,6 +31,9 @@
 
 namespace pde {
 
+// tensors per adasum call (a kernel-argument table of cumulative ends, like kMaxPackSegs: graph-capturable)
+constexpr int kMaxAdasumSegs = 96;
+
 class XgmiAllreduce {
  public:
   XgmiAllreduce(int rank, int size, int device, int64_t max_bytes, int blocks, double timeout_s);
@@ -47,6 +50,12 @@ class XgmiAllreduce {
   // carries 2/N of the bucket instead of all of it); same contract as allreduce.  An instance runs either form
   // only (their flag values differ), and a kernel folding the exchange in (view()) uses a one-shot instance.
   void allreduce_twoshot(const float* src, float* dst, int64_t n, float scale, hipStream_t s, bool wire_bf16 = false);
+  // hvd.Adasum of the N ranks' buffers (adasum_weights.h), per SEGMENT: segs are the element counts of the tensors
+  // fused in src (they sum to n; at most kMaxAdasumSegs, none empty) and every tensor gets its own dot products
+  // and norms.  dst[i] = scale * sum_r w_r(segment of i) * src_r[i]; fp32; src may alias dst; n * 4 <= max_bytes;
+  // a power-of-two world; one-shot instances only.  Two launches on `s` (Gram pass with the peer exchange, then
+  // weights + combine), both hipGraph-capturable; the result is bit-identical on all ranks.
+  void adasum(const float* src, float* dst, int64_t n, const std::vector<int64_t>& segs, float scale, hipStream_t s);
   XgmiView view() const;  // device view for kernels that fold the exchange in (xgmi_device.h)
   // test hook: every workgroup of this rank stalls `us` microseconds between its flag wait and its peer reads
   void set_read_delay_us(double us) { read_delay_ticks_ = static_cast<uint64_t>(us * 100.0); }
@@ -77,6 +86,7 @@ class XgmiAllreduce {
   uint32_t* state_ = nullptr;   // kXgmiStateWords: call epoch, done count, error word (device-local)
   uint32_t* host_ = nullptr;    // kXgmiHostWords, pinned host memory mapped into the device (status / abort)
   uint32_t* host_dev_ = nullptr;  // its device-side address
+  double* gram_ = nullptr;      // adasum: (blocks + kMaxAdasumSegs) rows of partial Gram matrices (device-local)
   std::vector<char*> peers_;    // mapped bases, peers_[rank_] == local_
   bool opened_ = false;
   int mode_ = 0;  // 0 unused, 1 one-shot, 2 two-shot

@@ -11,6 +11,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "adasum_weights.h"
 #include "xgmi_allreduce.h"
 #include "xgmi_device.h"
 
@@ -294,6 +295,225 @@ __global__ void k_scale(const float* src, float* dst, int64_t n, float scale) {
     dst[i] = src[i] * scale;
 }
 
+// ---- Adasum: Gram pass (with the peer exchange) + weights and combine --------------------------------------
+// adasum_weights.h: the Adasum tree of N rank vectors is sum_r w_r x_r with the w_r a function of the Gram matrix
+// G[i][j] = x_i . x_j alone -- per TENSOR (segment) of the fused buffer.  Both launches use the one-shot grid (one
+// workgroup per chunk, the same on every rank).  A PIECE is (segment s) x (chunk b); its partial Gram goes to
+// workspace row b + s: consecutive pieces advance b, s or both, so the row is unique, rows of one segment are
+// contiguous, and the last one is < blocks + kMaxAdasumSegs.
+constexpr int kGramMax = kXgmiMaxRanks * (kXgmiMaxRanks + 1) / 2;  // workspace row: packed upper triangle, <= 36
+constexpr int kWaves = kThreads / 64;
+
+struct AdasumSegs {
+  int count;
+  int64_t end[kMaxAdasumSegs];  // cumulative element ends; end[count - 1] == n
+};
+
+// [plo, phi) as a scalar head up to the next multiple of 4, a float4 body and a scalar tail: the split depends on
+// the indices alone (the slots are 4 KB aligned), so every rank walks a piece in the same order.
+#define PDE_PIECE_SPLIT(plo, phi)                                                      \
+  const int64_t a_lo = ((plo) + 3) / 4 * 4 < (phi) ? ((plo) + 3) / 4 * 4 : (phi);      \
+  const int64_t a_hi = (phi) / 4 * 4 > a_lo ? (phi) / 4 * 4 : a_lo
+
+// Launch 1.  VEC: the staging copy runs in float4 (src 16-byte aligned, n % 4 == 0); the slot reads do not depend
+// on it.  Products of fp32 values are exact in fp64 and the sums are fp64, reduced in a fixed order (per-thread
+// stride, wave shuffle, the workgroup's waves in order): no floating-point atomics, the same bits on every rank.
+template <int NR, bool VEC>
+__global__ __launch_bounds__(kThreads) void k_xgmi_adasum_gram(const float* src, int64_t n, XgmiView xv, int64_t chunk,
+                                                                AdasumSegs segs, double* gram) {
+  constexpr int NG = NR * (NR + 1) / 2;
+  __shared__ uint32_t s_epoch;
+  __shared__ int s_fail;
+  __shared__ double s_part[kWaves][NG];
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const uint32_t epoch = xgmi_epoch(xv, b, &s_epoch);
+  const int64_t lo = static_cast<int64_t>(b) * chunk;
+  const int64_t hi = lo + chunk < n ? lo + chunk : n;
+  float* mine = xgmi_slot(xv, xv.rank, epoch);
+  if (VEC) {
+    for (int64_t i = lo + 4 * tid; i < hi; i += 4 * kThreads)
+      *reinterpret_cast<float4*>(mine + i) = *reinterpret_cast<const float4*>(src + i);
+  } else {
+    for (int64_t i = lo + tid; i < hi; i += kThreads) mine[i] = src[i];
+  }
+  if (xgmi_publish_and_wait(xv, b, epoch, &s_fail)) {
+    xgmi_read_delay(xv);
+    const float* slots[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) slots[r] = xgmi_slot(xv, r, epoch);
+    int s = 0;
+    while (s < segs.count - 1 && segs.end[s] <= lo) ++s;  // the first segment that reaches into this chunk
+    for (int64_t plo = lo; plo < hi && s < segs.count; ++s) {
+      const int64_t phi = segs.end[s] < hi ? segs.end[s] : hi;
+      double g[NG];
+#pragma unroll
+      for (int k = 0; k < NG; ++k) g[k] = 0.0;
+      auto add = [&](const float (&x)[NR]) {
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < NR; ++i)
+#pragma unroll
+          for (int j = i; j < NR; ++j) g[k++] += static_cast<double>(x[i]) * static_cast<double>(x[j]);
+      };
+      auto add1 = [&](int64_t i) {
+        float x[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) x[r] = slots[r][i];
+        add(x);
+      };
+      PDE_PIECE_SPLIT(plo, phi);
+      for (int64_t i = plo + tid; i < a_lo; i += kThreads) add1(i);
+      for (int64_t i = a_lo + 4 * tid; i < a_hi; i += 4 * kThreads) {
+        float4 v[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) v[r] = *reinterpret_cast<const float4*>(slots[r] + i);
+        float x[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) x[r] = v[r].x;
+        add(x);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) x[r] = v[r].y;
+        add(x);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) x[r] = v[r].z;
+        add(x);
+#pragma unroll
+        for (int r = 0; r < NR; ++r) x[r] = v[r].w;
+        add(x);
+      }
+      for (int64_t i = a_hi + tid; i < phi; i += kThreads) add1(i);
+#pragma unroll
+      for (int k = 0; k < NG; ++k) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) g[k] += __shfl_down(g[k], off, 64);
+      }
+      if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < NG; ++k) s_part[tid >> 6][k] = g[k];
+      }
+      __syncthreads();
+      if (tid < NG) {
+        double t = s_part[0][tid];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) t += s_part[w][tid];
+        gram[static_cast<int64_t>(b + s) * kGramMax + tid] = t;
+      }
+      __syncthreads();  // s_part is reused by the next piece
+      plo = phi;
+    }
+  }
+  xgmi_finish(xv, b, epoch);
+}
+
+// Launch 2.  It RE-READS the peers' slots of the call launch 1 exchanged (no N-fold local copy).  They still hold
+// this call's bytes: a peer overwrites slot (e & 1) only in its call e + 2, which starts only after its call e + 1
+// saw this rank's flags of e + 1, i.e. after this rank launched call e + 1 -- and on this stream call e + 1 starts
+// behind this launch (the argument of xgmi_device.h, one launch further).  The epoch is the one launch 1's
+// xgmi_finish just stored.  A set error word (a timed-out or aborted wait, in this call or an earlier one not yet
+// cleared) means some chunk's Gram or bytes are missing: nothing is written, as the sum path drops its result.
+// Every workgroup sums the partial rows of the segments it touches in row order and derives the weights with the
+// same code from the same bits, on every rank; dst = scale * sum_r (float)w_r * slot_r[i] in rank order with
+// explicit fmas, so the scalar and float4 forms (VEC: dst 16-byte aligned) give the same bits too.
+template <int NR, bool VEC>
+__global__ __launch_bounds__(kThreads) void k_xgmi_adasum_combine(float* dst, int64_t n, float scale, XgmiView xv,
+                                                                   int64_t chunk, AdasumSegs segs, const double* gram) {
+  constexpr int NG = NR * (NR + 1) / 2;
+  __shared__ double s_G[NR * NR];
+  __shared__ double s_w[NR];
+  __shared__ float s_wf[NR];
+  __shared__ uint32_t s_state[2];
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (tid == 0) {  // one read per workgroup: every thread takes the same branch
+    s_state[0] = __hip_atomic_load(xv.state + kXgmiStateError, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_state[1] = __hip_atomic_load(xv.state + kXgmiStateEpoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (s_state[0] != 0u) return;
+  const uint32_t epoch = s_state[1];
+  const int64_t lo = static_cast<int64_t>(b) * chunk;
+  const int64_t hi = lo + chunk < n ? lo + chunk : n;
+  const float* slots[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) slots[r] = xgmi_slot(xv, r, epoch);
+  int s = 0;
+  while (s < segs.count - 1 && segs.end[s] <= lo) ++s;
+  for (int64_t plo = lo; plo < hi && s < segs.count; ++s) {
+    const int64_t phi = segs.end[s] < hi ? segs.end[s] : hi;
+    const int64_t seg_lo = s == 0 ? 0 : segs.end[s - 1];
+    const int64_t row0 = seg_lo / chunk + s, row1 = (segs.end[s] - 1) / chunk + s;
+    if (tid < NG) {
+      double t = gram[row0 * kGramMax + tid];
+      for (int64_t row = row0 + 1; row <= row1; ++row) t += gram[row * kGramMax + tid];
+      int i = 0, k = tid;  // packed upper-triangle index -> (i, j)
+      while (k >= NR - i) {
+        k -= NR - i;
+        ++i;
+      }
+      const int j = i + k;
+      s_G[i * NR + j] = t;
+      s_G[j * NR + i] = t;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      adasum_weights(s_G, NR, s_w);
+      for (int r = 0; r < NR; ++r) s_wf[r] = static_cast<float>(s_w[r]);
+    }
+    __syncthreads();
+    float w[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) w[r] = s_wf[r];
+    auto one = [&](int64_t i) {
+      float x[NR];
+#pragma unroll
+      for (int r = 0; r < NR; ++r) x[r] = slots[r][i];
+      float acc = w[0] * x[0];
+#pragma unroll
+      for (int r = 1; r < NR; ++r) acc = __fmaf_rn(w[r], x[r], acc);
+      dst[i] = acc * scale;
+    };
+    if (VEC) {
+      PDE_PIECE_SPLIT(plo, phi);
+      for (int64_t i = plo + tid; i < a_lo; i += kThreads) one(i);
+      for (int64_t i = a_lo + 4 * tid; i < a_hi; i += 4 * kThreads) {
+        float4 v[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) v[r] = *reinterpret_cast<const float4*>(slots[r] + i);
+        float4 acc = make_float4(w[0] * v[0].x, w[0] * v[0].y, w[0] * v[0].z, w[0] * v[0].w);
+#pragma unroll
+        for (int r = 1; r < NR; ++r) {
+          acc.x = __fmaf_rn(w[r], v[r].x, acc.x);
+          acc.y = __fmaf_rn(w[r], v[r].y, acc.y);
+          acc.z = __fmaf_rn(w[r], v[r].z, acc.z);
+          acc.w = __fmaf_rn(w[r], v[r].w, acc.w);
+        }
+        *reinterpret_cast<float4*>(dst + i) = make_float4(acc.x * scale, acc.y * scale, acc.z * scale, acc.w * scale);
+      }
+      for (int64_t i = a_hi + tid; i < phi; i += kThreads) one(i);
+    } else {
+      for (int64_t i = plo + tid; i < phi; i += kThreads) one(i);
+    }
+    plo = phi;
+  }
+}
+#undef PDE_PIECE_SPLIT
+
+template <int NR>
+void launch_adasum(bool vec_src, bool vec_dst, dim3 grid, hipStream_t s, const float* src, float* dst, int64_t n,
+                   float scale, const XgmiView& v, int64_t chunk, const AdasumSegs& segs, double* gram) {
+  if (vec_src)
+    hipLaunchKernelGGL((k_xgmi_adasum_gram<NR, true>), grid, dim3(kThreads), 0, s, src, n, v, chunk, segs, gram);
+  else
+    hipLaunchKernelGGL((k_xgmi_adasum_gram<NR, false>), grid, dim3(kThreads), 0, s, src, n, v, chunk, segs, gram);
+  if (vec_dst)
+    hipLaunchKernelGGL((k_xgmi_adasum_combine<NR, true>), grid, dim3(kThreads), 0, s, dst, n, scale, v, chunk, segs,
+                       gram);
+  else
+    hipLaunchKernelGGL((k_xgmi_adasum_combine<NR, false>), grid, dim3(kThreads), 0, s, dst, n, scale, v, chunk, segs,
+                       gram);
+}
+
 template <int NR, bool W>
 void launch_w(bool vec, dim3 grid, hipStream_t s, const float* src, float* dst, int64_t n, float scale,
               const XgmiView& v, int64_t chunk) {
@@ -337,6 +557,13 @@ XgmiAllreduce::XgmiAllreduce(int rank, int size, int device, int64_t max_bytes, 
   void* hd = nullptr;
   hip_check(hipHostGetDevicePointer(&hd, hp, 0), "hipHostGetDevicePointer");
   host_dev_ = static_cast<uint32_t*>(hd);
+  if (size > 1) {  // adasum's partial-Gram rows, sized once: never allocated during a (captured) call
+    const size_t gb = static_cast<size_t>(blocks + kMaxAdasumSegs) * kGramMax * sizeof(double);
+    void* gp = nullptr;
+    hip_check(hipMalloc(&gp, gb), "hipMalloc gram workspace");
+    gram_ = static_cast<double*>(gp);
+    hip_check(hipMemset(gram_, 0, gb), "zero gram workspace");
+  }
   hip_check(hipDeviceSynchronize(), "sync after init");  // flags are zero before any peer can map them
   peers_.assign(size, nullptr);
   peers_[rank] = local_;
@@ -449,6 +676,47 @@ void XgmiAllreduce::allreduce_twoshot(const float* src, float* dst, int64_t n, f
   ++calls_;
 }
 
+void XgmiAllreduce::adasum(const float* src, float* dst, int64_t n, const std::vector<int64_t>& segs, float scale,
+                           hipStream_t s) {
+  if (n <= 0) return;
+  if (n * 4 > max_bytes_) throw std::invalid_argument("xgmi adasum: bucket exceeds max_bytes");
+  if (mode_ == 2) throw std::logic_error("xgmi adasum: runs on a one-shot instance, not a two-shot one");
+  if ((size_ & (size_ - 1)) != 0) throw std::invalid_argument("xgmi adasum: the world size must be a power of two");
+  if (segs.empty() || static_cast<int>(segs.size()) > kMaxAdasumSegs)
+    throw std::invalid_argument("xgmi adasum: 1.." + std::to_string(kMaxAdasumSegs) + " segments per call");
+  AdasumSegs tab{};
+  tab.count = static_cast<int>(segs.size());
+  int64_t end = 0;
+  for (int i = 0; i < tab.count; ++i) {
+    if (segs[i] <= 0) throw std::invalid_argument("xgmi adasum: empty segment");
+    end += segs[i];
+    tab.end[i] = end;
+  }
+  if (end != n) throw std::invalid_argument("xgmi adasum: segment lengths do not sum to the element count");
+  mode_ = 1;
+  if (size_ == 1) {
+    const int g = static_cast<int>(std::min<int64_t>(1024, (n + kThreads - 1) / kThreads));
+    hipLaunchKernelGGL(k_scale, dim3(g), dim3(kThreads), 0, s, src, dst, n, scale);
+    hip_check(hipGetLastError(), "scale launch");
+    return;
+  }
+  if (!opened_) throw std::runtime_error("xgmi allreduce: peers not opened");
+  const XgmiView v = view();
+  // the one-shot grid (allreduce above): the same chunks on every rank
+  int64_t chunk = std::max<int64_t>((n + blocks_ - 1) / blocks_, 256);
+  chunk = ((chunk + 63) / 64) * 64;
+  const dim3 grid(static_cast<unsigned>((n + chunk - 1) / chunk));
+  const bool vec_src = (n % 4 == 0) && (reinterpret_cast<uintptr_t>(src) % 16 == 0);
+  const bool vec_dst = reinterpret_cast<uintptr_t>(dst) % 16 == 0;
+  switch (size_) {
+    case 2: launch_adasum<2>(vec_src, vec_dst, grid, s, src, dst, n, scale, v, chunk, tab, gram_); break;
+    case 4: launch_adasum<4>(vec_src, vec_dst, grid, s, src, dst, n, scale, v, chunk, tab, gram_); break;
+    default: launch_adasum<8>(vec_src, vec_dst, grid, s, src, dst, n, scale, v, chunk, tab, gram_); break;
+  }
+  hip_check(hipGetLastError(), "adasum launch");
+  ++calls_;
+}
+
 XgmiView XgmiAllreduce::view() const {
   if (size_ > 1 && !opened_) throw std::runtime_error("xgmi allreduce: peers not opened");
   XgmiView v{};
@@ -525,6 +793,8 @@ void XgmiAllreduce::close() {
   peers_.clear();
   retire(device_, local_);
   (void)hipFree(state_);
+  if (gram_ != nullptr) (void)hipFree(gram_);
+  gram_ = nullptr;
   if (host_ != nullptr) (void)hipHostFree(host_);
   local_ = nullptr;
   state_ = nullptr;

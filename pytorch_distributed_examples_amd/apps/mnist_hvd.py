@@ -52,6 +52,9 @@ def build_parser():
     ap.add_argument("--layers", action="store_true", help="GPU: layer-by-layer autograd path instead")
     ap.add_argument("--graph-chunk", type=int, default=50, help="GPU: training steps per hipGraph replay")
     ap.add_argument("--compression", default="none", choices=["none", "fp16", "bf16"])
+    ap.add_argument("--use-adasum", action="store_true",
+                    help="hvd.Adasum of the per-step weight deltas instead of averaged gradients (the upstream "
+                         "example's switch): layer-by-layer path, power-of-two worlds, no compression")
     add_runtime_args(ap)
     return ap
 
@@ -68,11 +71,15 @@ def main(argv=None):
     loader = ShardedLoader(train_set, args.batch_size, hvd.size(), hvd.rank(), shuffle=True)
 
     model = Net().to(dev)
-    fast = dev.type == "cuda" and not args.layers
+    fast = dev.type == "cuda" and not args.layers and not args.use_adasum
     optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
-    optimizer = hvd.DistributedOptimizer(optimizer, named_parameters=model.named_parameters(),
-                                         compression=getattr(hvd.Compression, "bf16" if args.compression == "none"
-                                                             and _cfg.grad_dtype == "bf16" else args.compression))
+    if args.use_adasum:  # (the fused step reduces gradients inside its kernel: Adasum takes the layer path)
+        optimizer = hvd.DistributedOptimizer(optimizer, named_parameters=model.named_parameters(),
+                                             compression=getattr(hvd.Compression, args.compression), op=hvd.Adasum)
+    else:
+        optimizer = hvd.DistributedOptimizer(optimizer, named_parameters=model.named_parameters(),
+                                             compression=getattr(hvd.Compression, "bf16" if args.compression == "none"
+                                                                 and _cfg.grad_dtype == "bf16" else args.compression))
     step = runner = None
     if fast:
         from ..hvd.cnn_step import FusedHvdStep
@@ -126,3 +133,4 @@ def main(argv=None):
     print(f"Worker: {hvd.rank()} | {seen / dt:.0f} images/s (this worker) | engine {hvd.engine_stats()}",
           flush=True)
     hvd.shutdown()
+    return model

@@ -12,7 +12,9 @@ is RCCL:
   through the c10d store) on a high-priority stream.
 
 Collectives return handles; ``synchronize(handle)`` orders the caller's stream after the collective (GPU)
-or blocks (CPU); engine failures raise :class:`HorovodInternalError`.  Environment knobs (Horovod names
+or blocks (CPU); engine failures raise :class:`HorovodInternalError`.  ``op=Adasum`` (:mod:`.adasum`): power-of-two
+worlds; CPU tensors through the fp64 tree over gloo, GPU tensors (fp32, one node) through the xGMI exchange's
+Adasum kernels -- per-tensor coefficients also inside a fused batch, no compression.  Environment knobs (Horovod names
 where one exists):
 
     HOROVOD_FUSION_THRESHOLD   fusion buffer bytes (default: xGMI policy, 64 MiB cap)
@@ -93,9 +95,17 @@ def _fusion_bytes(world: int) -> int:
 _retired: list = []
 
 
-def _py_allreduce(t, op):
+def _py_allreduce(t, op, seg_lengths=None):
     group = _ctx.engine_group
-    if op == ReduceOp.Average:
+    if op == ReduceOp.Adasum:
+        # CPU plane: all-gather the fused buffer, then the fp64 tree per tensor (seg_lengths: the tensors' extents)
+        from . import adasum
+
+        gathered = t.new_empty(_ctx.size * t.numel())
+        dist.all_gather_into_tensor(gathered, t, group=group)
+        adasum.adasum_segments_(gathered.view(_ctx.size, t.numel()), t,
+                                seg_lengths if seg_lengths is not None else [t.numel()])
+    elif op == ReduceOp.Average:
         dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
         t.div_(_ctx.size)
     else:
@@ -325,15 +335,37 @@ def _auto_name(prefix: str, name: str | None) -> str:
 def _resolve_op(average, op):
     if op is None:
         op = ReduceOp.Average if (average is None or average) else ReduceOp.Sum
-    if op == ReduceOp.Adasum:
-        raise NotImplementedError("Adasum is not supported; use Average or Sum")
+    if op == ReduceOp.Adasum and _ctx.size & (_ctx.size - 1):
+        raise ValueError(f"Adasum needs a power-of-two number of ranks, not {_ctx.size}")
+    return op
+
+
+def _adasum_op(op, tensor, compressed: bool = False):
+    """Adasum's limits, raised HERE (an engine-side failure would take the whole engine down): no compressed wire;
+    GPU tensors go through the xGMI exchange only -- fp32, one node, at most its ``max_bytes`` per tensor.  At
+    world 1 the tree is the tensor itself, i.e. a Sum (the pre/post scales still apply)."""
+    if op != ReduceOp.Adasum:
+        return op
+    if compressed:
+        raise ValueError("Adasum does not support compression")
+    if _ctx.size == 1:
+        return ReduceOp.Sum
+    if tensor.is_cuda:
+        if _ctx.xgmi is None:
+            raise RuntimeError("Adasum on GPU tensors needs the xGMI data plane (one node, PDE_HVD_DATA_PLANE=auto "
+                               "or xgmi); there is no RCCL form")
+        if tensor.dtype != torch.float32:
+            raise ValueError(f"Adasum on GPU tensors: fp32 only, not {tensor.dtype}")
+        if tensor.numel() * 4 > _ctx.xgmi.max_bytes:
+            raise ValueError(f"Adasum: a tensor of {tensor.numel() * 4} B exceeds the xGMI exchange's max_bytes "
+                             f"({_ctx.xgmi.max_bytes} B)")
     return op
 
 
 def allreduce_async_(tensor, average=None, name=None, op=None, prescale_factor=1.0, postscale_factor=1.0,
                      compression_bf16: bool = False):
     _need()
-    op = _resolve_op(average, op)
+    op = _adasum_op(_resolve_op(average, op), tensor, compression_bf16)
     t = tensor if tensor.is_contiguous() else tensor.contiguous()
     h = _enqueue(_ctx.engine.allreduce, t, t, _auto_name("allreduce", name), op, float(prescale_factor),
                  float(postscale_factor), compression_bf16)
@@ -343,7 +375,7 @@ def allreduce_async_(tensor, average=None, name=None, op=None, prescale_factor=1
 
 def allreduce_async(tensor, average=None, name=None, op=None, prescale_factor=1.0, postscale_factor=1.0):
     _need()
-    op = _resolve_op(average, op)
+    op = _adasum_op(_resolve_op(average, op), tensor)
     t = tensor.contiguous()
     out = torch.empty_like(t)
     h = _enqueue(_ctx.engine.allreduce, t, out, _auto_name("allreduce", name), op, float(prescale_factor),
@@ -354,6 +386,8 @@ def allreduce_async(tensor, average=None, name=None, op=None, prescale_factor=1.
 def allreduce(tensor, average=None, name=None, compression=None, op=None, prescale_factor=1.0,
               postscale_factor=1.0):
     if compression is not None:
+        if op == ReduceOp.Adasum and getattr(compression, "wire_bf16", True):
+            raise ValueError("Adasum does not support compression")
         c, ctx = compression.compress(tensor)
         out = synchronize(allreduce_async(c, average, name, op, prescale_factor, postscale_factor))
         return compression.decompress(out, ctx)
@@ -525,7 +559,16 @@ def allreduce_inline_(tensors, op=ReduceOp.Average, prescale_factor=1.0, postsca
     same call with the same tensors in the same order -- what a cached (already negotiated) tensor set
     guarantees; :meth:`DistributedOptimizer.enable_graph_mode` checks that first."""
     _need()
-    _enqueue(_ctx.engine.allreduce_inline, list(tensors), int(op), float(prescale_factor), float(postscale_factor),
+    tensors = list(tensors)
+    if op == ReduceOp.Adasum:
+        _resolve_op(None, op)
+        for t in tensors:
+            _adasum_op(op, t, bool(compression_bf16))
+        if _ctx.size == 1:  # the tree of one rank is the tensor: only the scales remain
+            if float(prescale_factor) * float(postscale_factor) != 1.0:
+                torch._foreach_mul_(tensors, float(prescale_factor) * float(postscale_factor))
+            return
+    _enqueue(_ctx.engine.allreduce_inline, tensors, int(op), float(prescale_factor), float(postscale_factor),
              bool(compression_bf16))
 
 

@@ -14,6 +14,12 @@ Used by the reference at horovod/mnist_horovod.py:53 and horovod/horovod_mnist_e
   parameter (one step negotiated through the engine), ``synchronize()`` enqueues the same fused batches on
   the caller's stream -- no engine thread, no host wait -- so the whole training step records into a hipGraph.
   SPMD: every rank must reach ``synchronize()`` each step (as with a captured DDP step).
+* ``op=Adasum`` (:mod:`.adasum`; power-of-two worlds) has Horovod's delta semantics and registers no gradient
+  hooks: ``step()`` keeps the starting weights, runs the wrapped optimizer's LOCAL step, Adasums the weight
+  deltas ``p - start`` -- one named tensor per parameter, so each gets its own coefficients; eager: all enqueued,
+  then synchronized; graph mode: one stream-ordered ``allreduce_inline_`` -- and sets ``p = start + delta``.
+  GPU tensors take the xGMI exchange's Adasum kernels (``XgmiAllreduce::adasum``).  No compression;
+  ``backward_passes_per_step`` needs nothing (local accumulation happens before ``step()``).
 * ``Compression.fp16`` sends fp32 gradients as bf16 on the wire (CDNA4's native 16-bit training format;
   same bytes as fp16, fp32 exponent range); ``Compression.bf16`` is the explicit name.
 """
@@ -85,6 +91,13 @@ class _DistributedOptimizerMixin:
         self._should_sync = True
         self._graph = False
         self._hooks = []
+        self._adasum = op == core.ReduceOp.Adasum
+        self._adasum_bufs = None
+        if self._adasum:
+            if getattr(compression, "wire_bf16", True):
+                raise ValueError("Adasum does not support gradient compression")
+            core._resolve_op(None, op)  # a world that is no power of two: ValueError here, not at the first step
+            return  # no gradient hooks: step() reduces the weight DELTAS
         if core.size() > 1:
             for _, p in named:
                 if p.requires_grad:
@@ -155,8 +168,57 @@ class _DistributedOptimizerMixin:
             self._counts[p] = 0
         self._synchronized = True
 
+    def _adasum_buffers(self):
+        """(params, start, delta): persistent per-parameter buffers (a replayed graph keeps pointing at them).  The
+        deltas are views of ONE flat buffer when the parameters share a dtype, so a fused batch is reduced in place
+        (the engine's adjacent-views route), without pack / unpack."""
+        if self._adasum_bufs is None:
+            params = [p for p in self._param_names if p.requires_grad]
+            start = [torch.empty_like(p, memory_format=torch.contiguous_format) for p in params]
+            if params and all(p.dtype == params[0].dtype and p.device == params[0].device for p in params):
+                flat = torch.empty(sum(p.numel() for p in params), dtype=params[0].dtype, device=params[0].device)
+                delta, off = [], 0
+                for p in params:
+                    delta.append(flat[off:off + p.numel()].view(p.shape))
+                    off += p.numel()
+            else:
+                delta = [torch.empty_like(s) for s in start]
+            self._adasum_bufs = (params, start, delta)
+        return self._adasum_bufs
+
+    @torch.no_grad()
+    def _adasum_step(self, closure):
+        """Horovod's Adasum optimizer: the wrapped optimizer steps on the LOCAL gradients, and what the ranks
+        combine is the weight change it made -- p = start + adasum_r(p_r - start), one named tensor per parameter
+        (so every parameter gets its own coefficients)."""
+        if core.size() == 1:  # the tree of one rank's delta is that delta
+            return super().step(closure)  # type: ignore[misc]
+        params, start, delta = self._adasum_buffers()
+        if not params:
+            return super().step(closure)  # type: ignore[misc]
+        if params[0].is_cuda:  # gradients may still be in flight on the wgrad side stream
+            streams.join(params[0].device)
+        torch._foreach_copy_(start, params)
+        loss = super().step(closure)  # type: ignore[misc]
+        torch._foreach_copy_(delta, params)
+        torch._foreach_sub_(delta, start)
+        if self._graph:
+            core.allreduce_inline_(delta, core.ReduceOp.Adasum)
+        else:
+            try:
+                hs = [core.allreduce_async_(d, name=self._param_names[p], op=core.ReduceOp.Adasum)
+                      for p, d in zip(params, delta)]
+                for h in hs:
+                    core.synchronize(h)
+            except HorovodInternalError:
+                torch._foreach_copy_(params, start)  # leave the weights of the last completed step
+                raise
+        torch._foreach_copy_(params, start)
+        torch._foreach_add_(params, delta)
+        return loss
+
     def synchronize(self):
-        if core.size() == 1:
+        if core.size() == 1 or self._adasum:  # (Adasum: nothing is in flight before step())
             self._synchronized = True
             return
         if self._graph:
@@ -189,6 +251,9 @@ class _DistributedOptimizerMixin:
             self._should_sync = True
 
     def step(self, closure=None):
+        if self._adasum:
+            self._synchronized = False
+            return self._adasum_step(closure)
         if self._should_sync:
             if self._synchronized:
                 pass

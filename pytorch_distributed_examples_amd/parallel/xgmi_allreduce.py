@@ -75,6 +75,18 @@ class XgmiAllreduce:
             self.impl.allreduce_(t, 1.0 / self.size if avg else 1.0, wire_bf16)
         return t
 
+    def adasum_(self, t: torch.Tensor, seg_lengths=None, scale: float = 1.0) -> torch.Tensor:
+        """In-place ``hvd.Adasum`` of the ranks' fp32 tensors (:mod:`..hvd.adasum`): a Gram pass over the peers'
+        staged copies, then the tree's weights and ``scale * sum_r w_r x_r`` -- two launches, stream-ordered,
+        hipGraph-capturable, bit-identical on all ranks.  ``seg_lengths``: the element counts of the tensors fused
+        in ``t`` (each gets its own dot products and norms); default: ``t`` is one tensor.  Power-of-two worlds,
+        one-shot instances only."""
+        if self.two_shot:
+            raise RuntimeError("xGMI Adasum runs on a one-shot instance (two_shot=False)")
+        segs = [int(t.numel())] if seg_lengths is None else [int(n) for n in seg_lengths]
+        self.impl.adasum_(t, segs, float(scale))
+        return t
+
     def view(self) -> list:
         """Flat device view (csrc/comm/xgmi_view.h) for kernels that fold the exchange into their own
         epilogue: the fused CNN's gradient reduction (``FusedCNN.forward_backward(..., xgmi=self)``)."""
