@@ -1176,50 +1176,81 @@ Tensor embbag_bwd(const Tensor& dy, const Tensor& idx, const Tensor& off, int64_
 // ------------------------------------------------------------------------------------------------
 // Fused MNIST CNN training step
 // ------------------------------------------------------------------------------------------------
-// Launches forward+loss+backward for the whole batch; returns (loss scalar, slabs).  The caller reduces
-// the slabs into a gradient buffer with cnn_reduce (possibly the DDP flat gradient).
-Tensor cnn_train(const Tensor& images, const Tensor& tgt, const Tensor& params, Tensor& rng, double p_drop2,
-                 double p_drop1, bool training, Tensor& grads, bool accumulate, const optional<Tensor>& gscale,
-                 const optional<Tensor>& stamps, const optional<Tensor>& frag_buf, bool prep,
-                 const optional<Tensor>& sgd_hp, int64_t stop_after, const optional<Tensor>& sgd_step,
-                 const optional<std::vector<int64_t>>& xgmi_view, double xscale, int64_t opt_mode,
-                 const optional<Tensor>& opt_m, const optional<Tensor>& opt_v) {
-  CHECK_IN(images); CHECK_IN(tgt); CHECK_IN(params); CHECK_IN(rng); CHECK_IN(grads);
-  // the stateful updates in the reduction (1 SGD + momentum / weight decay, 2 Adam, 3 AdamW): hyper-parameters,
-  // step words and flat state buffers shaped like params
-  TORCH_CHECK(opt_mode >= 0 && opt_mode <= 3, "cnn_train: opt_mode must be 0..3");
-  const bool have_m = opt_m.has_value() && opt_m->defined(), have_v = opt_v.has_value() && opt_v->defined();
-  if (opt_mode != 0) {
-    TORCH_CHECK(sgd_hp.has_value() && sgd_hp->defined() && sgd_step.has_value() && sgd_step->defined(),
-                "cnn_train: opt_mode != 0 needs sgd_hp and sgd_step");
-    TORCH_CHECK(sgd_step->is_cuda() && sgd_step->scalar_type() == at::kInt && sgd_step->numel() >= 2,
-                "cnn_train: opt_mode != 0 needs step int32[2]");
-    TORCH_CHECK(have_m, "cnn_train: opt_mode != 0 needs opt_m (momentum_buffer / exp_avg)");
-    TORCH_CHECK(opt_mode < 2 || have_v, "cnn_train: Adam / AdamW need opt_v (exp_avg_sq)");
-  }
-  for (const Tensor* t : {have_m ? &*opt_m : nullptr, have_v ? &*opt_v : nullptr}) {
-    if (t == nullptr) continue;
-    CHECK_IN(*t); CHECK_F32(*t);
-    TORCH_CHECK(t->numel() == pde::cnn_num_params() && t->device() == params.device(),
-                "cnn_train: optimiser state must be flat fp32 buffers shaped like params, on their device");
-  }
+// XgmiAllreduce.view(): base[8], state, timeout_ticks, flag_bytes, slot_bytes, rank, size, blocks, read_delay_ticks,
+// host -- the in-launch gradient exchange of cnn_train and mlp_train (world > 1, one node)
+pde::XgmiView xgmi_view_from(const std::vector<int64_t>& w, const char* who) {
+  TORCH_CHECK(w.size() == pde::kXgmiMaxRanks + 9, who, ": malformed xgmi view");
   pde::XgmiView xv{};
-  const bool have_xv = xgmi_view.has_value();
-  if (have_xv) {  // XgmiAllreduce.view(): base[8], state, timeout_ticks, flag_bytes, slot_bytes, rank, size, blocks,
-                  // read_delay_ticks, host
-    const auto& w = *xgmi_view;
-    TORCH_CHECK(w.size() == pde::kXgmiMaxRanks + 9, "cnn_train: malformed xgmi view");
-    for (int r = 0; r < pde::kXgmiMaxRanks; ++r) xv.base[r] = reinterpret_cast<char*>(w[r]);
-    xv.state = reinterpret_cast<uint32_t*>(w[8]);
-    xv.timeout_ticks = static_cast<uint64_t>(w[9]);
-    xv.flag_bytes = w[10];
-    xv.slot_bytes = w[11];
-    xv.rank = static_cast<int>(w[12]);
-    xv.size = static_cast<int>(w[13]);
-    xv.blocks = static_cast<int>(w[14]);
-    xv.read_delay_ticks = static_cast<uint64_t>(w[15]);
-    xv.host = reinterpret_cast<uint32_t*>(w[16]);
+  for (int r = 0; r < pde::kXgmiMaxRanks; ++r) xv.base[r] = reinterpret_cast<char*>(w[r]);
+  xv.state = reinterpret_cast<uint32_t*>(w[8]);
+  xv.timeout_ticks = static_cast<uint64_t>(w[9]);
+  xv.flag_bytes = w[10];
+  xv.slot_bytes = w[11];
+  xv.rank = static_cast<int>(w[12]);
+  xv.size = static_cast<int>(w[13]);
+  xv.blocks = static_cast<int>(w[14]);
+  xv.read_delay_ticks = static_cast<uint64_t>(w[15]);
+  xv.host = reinterpret_cast<uint32_t*>(w[16]);
+  return xv;
+}
+
+void check_cnn_frag(const Tensor& frag, const char* who) {
+  CHECK_IN(frag);
+  TORCH_CHECK(frag.nbytes() >= pde::cnn_frag_bytes() && reinterpret_cast<uintptr_t>(frag.data_ptr()) % 16 == 0, who,
+              ": frag must be a 16-B aligned buffer of cnn_frag_bytes()");
+}
+
+// The update descriptor of cnn_train and cnn_opt from their tensors (mode: pde::CnnUpdateMode).  pde::
+// cnn_update_valid's rules with a message each, plus what only a tensor can tell: hp, step and the state are
+// contiguous on params' device, hp fp32[HP_COUNT], step int32 ([2] for the stateful modes), m / v fp32 shaped like
+// params.
+pde::CnnUpdate cnn_update_from(const Tensor& params, int64_t mode, const optional<Tensor>& hp,
+                               const optional<Tensor>& step, const optional<Tensor>& m, const optional<Tensor>& v,
+                               const char* who) {
+  const auto have = [](const optional<Tensor>& t) { return t.has_value() && t->defined(); };
+  const auto on_dev = [&](const Tensor& t) {
+    return t.is_cuda() && t.is_contiguous() && t.device() == params.device();
+  };
+  TORCH_CHECK(mode >= pde::CNN_SGD && mode <= pde::CNN_ADAMW, who,
+              ": mode must be 0..3 (plain SGD, SGD with state, Adam, AdamW)");
+  const bool stateful = mode != pde::CNN_SGD;
+  if (stateful) {
+    TORCH_CHECK(have(hp) && have(step), who, ": a stateful mode needs hp and step");
+    TORCH_CHECK(have(m), who, ": a stateful mode needs m (momentum_buffer / exp_avg)");
+    TORCH_CHECK(mode < pde::CNN_ADAM || have(v), who, ": Adam / AdamW need v (exp_avg_sq)");
+  }
+  if (have(hp))
+    TORCH_CHECK(on_dev(*hp) && hp->scalar_type() == at::kFloat && hp->numel() >= pde::HP_COUNT, who,
+                ": hp must hold the optimiser's fp32 hyper-parameters, on the parameters' device");
+  if (have(step))
+    TORCH_CHECK(on_dev(*step) && step->scalar_type() == at::kInt && step->numel() >= (stateful ? 2 : 1), who,
+                ": step must be a device int32 tensor ([2] for a stateful mode)");
+  for (const optional<Tensor>* t : {&m, &v})
+    if (have(*t))
+      TORCH_CHECK(on_dev(**t) && (*t)->scalar_type() == at::kFloat && (*t)->numel() == pde::cnn_num_params(), who,
+                  ": optimiser state must be flat fp32 buffers shaped like params, on their device");
+  const pde::CnnUpdate u{static_cast<int>(mode), cf32(hp), have(step) ? step->data_ptr<int>() : nullptr, f32(m),
+                         f32(v)};
+  TORCH_INTERNAL_ASSERT(pde::cnn_update_valid(u));
+  return u;
+}
+
+// One training step: forward + loss + backward of the whole batch, the gradients reduced (with xgmi_view: exchanged
+// with the peers and summed) into grads, and with hp the update of `mode` applied in that reduction; returns the
+// loss scalar.  The slabs and the activation image are temporaries of the call.
+Tensor cnn_train(const Tensor& images, const Tensor& tgt, const Tensor& params, Tensor& rng, double p_drop2,
+                 double p_drop1, bool training, Tensor& grads, bool accumulate, const optional<Tensor>& stamps,
+                 const optional<Tensor>& frag_buf, bool prep, const optional<Tensor>& hp, int64_t stop_after,
+                 const optional<Tensor>& step, const optional<std::vector<int64_t>>& xgmi_view, double xscale,
+                 int64_t mode, const optional<Tensor>& m, const optional<Tensor>& v) {
+  CHECK_IN(images); CHECK_IN(tgt); CHECK_IN(params); CHECK_IN(rng); CHECK_IN(grads);
+  pde::CnnTrainArgs a{};
+  a.update = cnn_update_from(params, mode, hp, step, m, v, "cnn_train");
+  pde::XgmiView xv{};
+  if (xgmi_view.has_value()) {
+    xv = xgmi_view_from(*xgmi_view, "cnn_train");
     TORCH_CHECK(!accumulate, "cnn_train: the xGMI gradient exchange replaces accumulation");
+    a.xv = &xv;
   }
   CHECK_F32(images); CHECK_F32(params); CHECK_F32(grads);
   TORCH_CHECK(params.numel() == pde::cnn_num_params(), "cnn_train: params must be the flat Net parameters");
@@ -1230,7 +1261,8 @@ Tensor cnn_train(const Tensor& images, const Tensor& tgt, const Tensor& params, 
   const int B = tgt.numel();
   const int ni = pde::cnn_images_per_workgroup();
   const int n = (B + ni - 1) / ni;
-  if (stamps.has_value() && stamps->defined())
+  const bool have_stamps = stamps.has_value() && stamps->defined();
+  if (have_stamps)
     TORCH_CHECK(stamps->numel() >= static_cast<long>(n) * 16 && stamps->scalar_type() == at::kLong,
                 "cnn_train: stamps must be int64[nwg*16]");
   auto fo = images.options();
@@ -1241,32 +1273,22 @@ Tensor cnn_train(const Tensor& images, const Tensor& tgt, const Tensor& params, 
   Tensor frag;
   if (frag_buf.has_value() && frag_buf->defined()) {
     frag = *frag_buf;
-    CHECK_IN(frag);
-    TORCH_CHECK(frag.nbytes() >= pde::cnn_frag_bytes() && reinterpret_cast<uintptr_t>(frag.data_ptr()) % 16 == 0,
-                "cnn_train: frag must be a 16-B aligned buffer of cnn_frag_bytes()");
+    check_cnn_frag(frag, "cnn_train");
   } else {
     TORCH_CHECK(prep, "cnn_train: prep=False needs a persistent frag buffer");
     frag = at::empty({static_cast<long>(pde::cnn_frag_bytes())}, fo.dtype(at::kByte));
   }
-  if (sgd_hp.has_value() && sgd_hp->defined()) {
-    CHECK_IN(*sgd_hp); CHECK_F32(*sgd_hp);
-    TORCH_CHECK(sgd_hp->numel() >= pde::HP_COUNT, "cnn_train: sgd_hp must hold the optimiser hyper-parameters");
-  }
-  check(pde::cnn_train_fused(images.data_ptr<float>(), tgt.data_ptr<int64_t>(), B, params.data_ptr<float>(),
-                             frag.data_ptr(),
-                             reinterpret_cast<unsigned long long*>(rng.data_ptr()), static_cast<float>(p_drop2),
-                             static_cast<float>(p_drop1), training ? 1 : 0, slabs.data_ptr<float>(),
-                             part.data_ptr<float>(), reinterpret_cast<uint16_t*>(acts.data_ptr()), n, loss.data_ptr<float>(), grads.data_ptr<float>(), cf32(gscale),
-                             accumulate ? 1 : 0, cur_stream(),
-                             stamps.has_value() && stamps->defined()
-                                 ? reinterpret_cast<unsigned long long*>(stamps->data_ptr())
-                                 : nullptr,
-                             prep ? 1 : 0, sgd_hp.has_value() && sgd_hp->defined() ? sgd_hp->data_ptr<float>() : nullptr,
-                             static_cast<int>(stop_after),
-                             sgd_step.has_value() && sgd_step->defined() ? sgd_step->data_ptr<int>() : nullptr,
-                             have_xv ? &xv : nullptr, static_cast<float>(xscale), static_cast<int>(opt_mode),
-                             f32(opt_m), f32(opt_v)),
-        "cnn_train");
+  a.images = images.data_ptr<float>(); a.tgt = tgt.data_ptr<int64_t>(); a.B = B;
+  a.params = params.data_ptr<float>(); a.frag = frag.data_ptr();
+  a.rng = reinterpret_cast<unsigned long long*>(rng.data_ptr());
+  a.slabs = slabs.data_ptr<float>(); a.loss_part = part.data_ptr<float>(); a.acts = u16(acts); a.nwg = n;
+  a.loss = loss.data_ptr<float>(); a.grads = grads.data_ptr<float>();
+  a.p_drop2 = static_cast<float>(p_drop2); a.p_drop1 = static_cast<float>(p_drop1);
+  a.training = training ? 1 : 0; a.accumulate = accumulate ? 1 : 0; a.prep = prep ? 1 : 0;
+  a.stamps = have_stamps ? reinterpret_cast<unsigned long long*>(stamps->data_ptr()) : nullptr;
+  a.stop_after = static_cast<int>(stop_after);
+  a.xscale = static_cast<float>(xscale);
+  check(pde::cnn_train_fused(a, cur_stream()), "cnn_train");
   return loss;
 }
 
@@ -1276,15 +1298,14 @@ Tensor cnn_train(const Tensor& images, const Tensor& tgt, const Tensor& params, 
 std::tuple<Tensor, Tensor> cnn_eval(const Tensor& images, const optional<Tensor>& tgt, const Tensor& params,
                                     Tensor& frag, bool prep, bool want_pred, bool want_logp,
                                     const optional<Tensor>& stats) {
-  CHECK_IN(images); CHECK_IN(params); CHECK_IN(frag);
+  CHECK_IN(images); CHECK_IN(params);
   CHECK_F32(images); CHECK_F32(params);
   TORCH_CHECK(params.numel() == pde::cnn_num_params(), "cnn_eval: params must be the flat Net parameters");
   TORCH_CHECK(images.numel() > 0 && images.numel() % (28 * 28) == 0, "cnn_eval: images must be [B,1,28,28]");
   const int64_t B64 = images.numel() / (28 * 28);
   TORCH_CHECK(B64 <= (1 << 30), "cnn_eval: batch too large");
   const int B = static_cast<int>(B64);
-  TORCH_CHECK(frag.nbytes() >= pde::cnn_frag_bytes() && reinterpret_cast<uintptr_t>(frag.data_ptr()) % 16 == 0,
-              "cnn_eval: frag must be a 16-B aligned buffer of cnn_frag_bytes()");
+  check_cnn_frag(frag, "cnn_eval");
   const bool have_tgt = tgt.has_value() && tgt->defined();
   if (have_tgt) {
     CHECK_IN(*tgt);
@@ -1423,18 +1444,7 @@ void mlp_train(const Tensor& x, const Tensor& y, const std::vector<Tensor>& w, c
   a.xchg = 0;
   a.xscale = 1.f;
   if (xgmi_view.has_value()) {  // XgmiAllreduce.view(): the in-launch gradient exchange (world > 1, one node)
-    const auto& v = *xgmi_view;
-    TORCH_CHECK(v.size() == pde::kXgmiMaxRanks + 9, "mlp_train: malformed xgmi view");
-    for (int r = 0; r < pde::kXgmiMaxRanks; ++r) a.xv.base[r] = reinterpret_cast<char*>(v[r]);
-    a.xv.state = reinterpret_cast<uint32_t*>(v[8]);
-    a.xv.timeout_ticks = static_cast<uint64_t>(v[9]);
-    a.xv.flag_bytes = v[10];
-    a.xv.slot_bytes = v[11];
-    a.xv.rank = static_cast<int>(v[12]);
-    a.xv.size = static_cast<int>(v[13]);
-    a.xv.blocks = static_cast<int>(v[14]);
-    a.xv.read_delay_ticks = static_cast<uint64_t>(v[15]);
-    a.xv.host = reinterpret_cast<uint32_t*>(v[16]);
+    a.xv = xgmi_view_from(*xgmi_view, "mlp_train");
     a.xchg = 1;
     a.xscale = static_cast<float>(xscale);
     int ins[pde::kMlpMaxLayers], outs[pde::kMlpMaxLayers];
@@ -1451,68 +1461,18 @@ void mlp_train(const Tensor& x, const Tensor& y, const std::vector<Tensor>& w, c
   check(pde::mlp_train_step(a, grid, cur_stream()), "mlp_train");
 }
 
-// Plain SGD on the flat CNN parameters + fragment-image refresh (after the gradient all-reduce).
-}  // namespace
-namespace pde {
-// (declared here, not in pde_kernels.h: cnn_fused.hip is the only definition, bindings.cpp the only caller)
-hipError_t cnn_adamw_fused(float* params, const float* grads, float* m, float* v, const float* hp, void* frag,
-                           int* step, hipStream_t s);
-}  // namespace pde
-namespace {
-
-// AdamW over the flat CNN parameters + fragment refresh, one launch (FusedCNN.adamw_step)
-void cnn_adamw(Tensor& params, const Tensor& grads, Tensor& m, Tensor& v, const Tensor& hp, Tensor& frag,
-               Tensor& step) {
-  CHECK_IN(params); CHECK_IN(grads); CHECK_IN(m); CHECK_IN(v); CHECK_IN(hp); CHECK_IN(frag);
-  CHECK_F32(params); CHECK_F32(grads); CHECK_F32(m); CHECK_F32(v); CHECK_F32(hp);
-  const long n = pde::cnn_num_params();
-  TORCH_CHECK(params.numel() == n && grads.numel() == n && m.numel() == n && v.numel() == n, "cnn_adamw: sizes");
-  TORCH_CHECK(hp.numel() >= pde::HP_COUNT, "cnn_adamw: hp");
-  TORCH_CHECK(frag.nbytes() >= pde::cnn_frag_bytes(), "cnn_adamw: frag size");
-  TORCH_CHECK(step.is_cuda() && step.scalar_type() == at::kInt && step.numel() >= 2, "cnn_adamw: step int32[2]");
-  check(pde::cnn_adamw_fused(params.data_ptr<float>(), grads.data_ptr<float>(), m.data_ptr<float>(),
-                             v.data_ptr<float>(), hp.data_ptr<float>(), frag.data_ptr(), step.data_ptr<int>(),
-                             cur_stream()),
-        "cnn_adamw");
-}
-
-// The stateful updates over the flat CNN parameters + fragment refresh, one launch (FusedCNN.opt_step).  mode: the
-// optimiser kernels' (0 SGD with momentum / weight decay -- m: the momentum buffers, no v; 1 Adam; 2 AdamW)
-void cnn_opt(Tensor& params, const Tensor& grads, Tensor& m, const optional<Tensor>& v, const Tensor& hp, Tensor& frag,
-             Tensor& step, int64_t mode) {
-  CHECK_IN(params); CHECK_IN(grads); CHECK_IN(m); CHECK_IN(hp); CHECK_IN(frag);
-  CHECK_F32(params); CHECK_F32(grads); CHECK_F32(m); CHECK_F32(hp);
-  TORCH_CHECK(mode >= 0 && mode <= 2, "cnn_opt: mode must be 0..2");
-  const long n = pde::cnn_num_params();
-  TORCH_CHECK(params.numel() == n && grads.numel() == n && m.numel() == n, "cnn_opt: sizes");
-  const bool have_v = v.has_value() && v->defined();
-  TORCH_CHECK(mode == 0 || have_v, "cnn_opt: Adam / AdamW need v (exp_avg_sq)");
-  if (have_v) {
-    CHECK_IN(*v); CHECK_F32(*v);
-    TORCH_CHECK(v->numel() == n && v->device() == params.device(), "cnn_opt: v size / device");
-  }
-  TORCH_CHECK(m.device() == params.device() && grads.device() == params.device(), "cnn_opt: devices");
-  TORCH_CHECK(hp.numel() >= pde::HP_COUNT, "cnn_opt: hp");
-  TORCH_CHECK(frag.nbytes() >= pde::cnn_frag_bytes() && reinterpret_cast<uintptr_t>(frag.data_ptr()) % 16 == 0,
-              "cnn_opt: frag size / alignment");
-  TORCH_CHECK(step.is_cuda() && step.scalar_type() == at::kInt && step.numel() >= 2, "cnn_opt: step int32[2]");
-  check(pde::cnn_opt_fused(params.data_ptr<float>(), grads.data_ptr<float>(), m.data_ptr<float>(), f32(v),
-                           hp.data_ptr<float>(), frag.data_ptr(), step.data_ptr<int>(), static_cast<int>(mode),
-                           cur_stream()),
+// The update of `mode` over the flat CNN parameters + the fragment-image refresh, ONE launch, after a gradient
+// all-reduce that ran outside the reduction kernel (FusedCNN.opt_step).  step may be None for plain SGD.
+void cnn_opt(Tensor& params, const Tensor& grads, Tensor& frag, const Tensor& hp, const optional<Tensor>& step,
+             int64_t mode, const optional<Tensor>& m, const optional<Tensor>& v) {
+  CHECK_IN(params); CHECK_IN(grads); CHECK_F32(params); CHECK_F32(grads);
+  TORCH_CHECK(params.numel() == pde::cnn_num_params() && grads.numel() == params.numel() &&
+                  grads.device() == params.device(),
+              "cnn_opt: params and grads must be the flat Net parameters and their gradient, on one device");
+  check_cnn_frag(frag, "cnn_opt");
+  const pde::CnnUpdate u = cnn_update_from(params, mode, hp, step, m, v, "cnn_opt");
+  check(pde::cnn_opt_fused(params.data_ptr<float>(), grads.data_ptr<float>(), frag.data_ptr(), u, cur_stream()),
         "cnn_opt");
-}
-
-void cnn_sgd(Tensor& params, const Tensor& grads, const Tensor& hp, Tensor& frag, const optional<Tensor>& step) {
-  CHECK_IN(params); CHECK_IN(grads); CHECK_IN(hp); CHECK_IN(frag);
-  CHECK_F32(params); CHECK_F32(grads); CHECK_F32(hp);
-  TORCH_CHECK(params.numel() == pde::cnn_num_params() && grads.numel() == pde::cnn_num_params(), "cnn_sgd: sizes");
-  TORCH_CHECK(hp.numel() >= pde::HP_COUNT, "cnn_sgd: hp");
-  TORCH_CHECK(frag.nbytes() >= pde::cnn_frag_bytes(), "cnn_sgd: frag size");
-  if (step.has_value() && step->defined())
-    TORCH_CHECK(step->is_cuda() && step->scalar_type() == at::kInt, "cnn_sgd: step must be a device int32 tensor");
-  check(pde::cnn_sgd_fused(params.data_ptr<float>(), grads.data_ptr<float>(), hp.data_ptr<float>(), frag.data_ptr(),
-                           cur_stream(), step.has_value() && step->defined() ? step->data_ptr<int>() : nullptr),
-        "cnn_sgd");
 }
 
 }  // namespace
@@ -1520,12 +1480,12 @@ void cnn_sgd(Tensor& params, const Tensor& grads, const Tensor& hp, Tensor& frag
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cnn_train", &cnn_train, py::arg("images"), py::arg("tgt"), py::arg("params"), py::arg("rng"),
         py::arg("p_drop2"), py::arg("p_drop1"), py::arg("training"), py::arg("grads"), py::arg("accumulate"),
-        py::arg("gscale") = py::none(), py::arg("stamps") = py::none(), py::arg("frag") = py::none(),
-        py::arg("prep") = true, py::arg("sgd_hp") = py::none(), py::arg("stop_after") = -1,
-        py::arg("sgd_step") = py::none(), py::arg("xgmi_view") = py::none(), py::arg("xscale") = 1.0,
-        py::arg("opt_mode") = 0, py::arg("opt_m") = py::none(), py::arg("opt_v") = py::none());
-  m.def("cnn_opt", &cnn_opt, py::arg("params"), py::arg("grads"), py::arg("m"), py::arg("v"), py::arg("hp"),
-        py::arg("frag"), py::arg("step"), py::arg("mode"));
+        py::kw_only(), py::arg("stamps") = py::none(), py::arg("frag") = py::none(), py::arg("prep") = true,
+        py::arg("hp") = py::none(), py::arg("stop_after") = -1, py::arg("step") = py::none(),
+        py::arg("xgmi_view") = py::none(), py::arg("xscale") = 1.0, py::arg("mode") = 0, py::arg("m") = py::none(),
+        py::arg("v") = py::none());
+  m.def("cnn_opt", &cnn_opt, py::arg("params"), py::arg("grads"), py::arg("frag"), py::arg("hp"), py::arg("step"),
+        py::arg("mode"), py::arg("m") = py::none(), py::arg("v") = py::none());
   m.def("mlp_train_grid", &mlp_train_grid_py);
   m.def("mlp_train", &mlp_train, py::arg("x"), py::arg("y"), py::arg("w"), py::arg("b"), py::arg("gw"), py::arg("gb"),
         py::arg("mw"), py::arg("vw"), py::arg("mb"), py::arg("vb"), py::arg("wbf"), py::arg("wtbf"), py::arg("act"),
@@ -1533,10 +1493,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("loss"), py::arg("hp"), py::arg("step"), py::arg("mode"), py::arg("bar"), py::arg("err"),
         py::arg("grid"), py::arg("stamps") = py::none(), py::arg("xgmi_view") = py::none(),
         py::arg("xscale") = 1.0);
-  m.def("cnn_adamw", &cnn_adamw, py::arg("params"), py::arg("grads"), py::arg("m"), py::arg("v"), py::arg("hp"),
-        py::arg("frag"), py::arg("step"));
-  m.def("cnn_sgd", &cnn_sgd, py::arg("params"), py::arg("grads"), py::arg("hp"), py::arg("frag"),
-        py::arg("step") = py::none());
   m.def("clear_last_error", []() { return static_cast<int>(hipGetLastError()); },
         "Read and reset the HIP last-error state (after an aborted stream capture).");
   m.def("bn_reserve_headroom", &pde::bn_reserve_headroom, py::arg("blocks"),

@@ -304,40 +304,68 @@ hipError_t embbag_fwd(const float* w, const int64_t* idx, const int64_t* off, in
 int cnn_num_params();
 size_t cnn_smem_bytes();
 int cnn_images_per_workgroup();
-// Three launches: the weight-fragment prep, the fused training kernel (per-workgroup gradient slabs +
-// loss partials), then the deterministic slab reduction into `grads` (16-B aligned; (+)= gscale * sum)
-// which also finalises the loss and advances the dropout counter.
-size_t cnn_frag_bytes();  // workspace for the per-step bf16 weight-fragment image (16-B aligned)
-// prep = 0 skips the fragment prep (the image is already current: the previous step's fused SGD wrote it).
-// sgd_hp != nullptr fuses plain SGD (lr = sgd_hp[HP_LR], grad scale sgd_hp[HP_GRAD_SCALE]) and the
-// fragment refresh into the slab reduction.  xv (world > 1, an XgmiAllreduce's view): the reduction
-// first exchanges each workgroup's gradient chunk with every peer over xGMI and sums all ranks' chunks in
-// rank order (x xscale), so the update stays fused at any world size -- 2 launches per step.
-int cnn_slab_floats();  // per-workgroup slab (every gradient except fc1's weight)
-int cnn_act_rows();     // rows of the per-batch activation image feeding the fc1 weight-gradient GEMM
+size_t cnn_frag_bytes();  // the bf16 weight-fragment image the kernels read the conv weights from (16-B aligned)
+int cnn_slab_floats();    // per-workgroup slab (every gradient except fc1's weight)
+int cnn_act_rows();       // rows of the per-batch activation image feeding the fc1 weight-gradient GEMM
 int cnn_act_pitch(int nwg);  // its row pitch (bf16 elements)
-hipError_t cnn_train_fused(const float* images, const int64_t* tgt, int B, float* params, void* frag,
-                           unsigned long long* rng, float p_drop2, float p_drop1, int training, float* slabs,
-                           float* loss_part, uint16_t* acts, int nwg, float* loss, float* grads, const float* gscale,
-                           int accumulate, hipStream_t s, unsigned long long* stamps = nullptr, int prep = 1,
-                           const float* sgd_hp = nullptr, int stop_after = -1, int* sgd_step = nullptr,
-                           const XgmiView* xv = nullptr, float xscale = 1.f, int opt_mode = 0,
-                           float* opt_m = nullptr, float* opt_v = nullptr);
-// opt_mode: the update fused into the slab reduction when sgd_hp != nullptr.  0 plain SGD (above); 1 SGD with
-// momentum and / or L2 weight decay; 2 Adam (L2); 3 AdamW -- the optimiser's own update function (optim_device.h)
-// on the final gradient, its state in flat fp32 buffers indexed like params: opt_m (momentum_buffer / exp_avg) and
-// opt_v (exp_avg_sq, modes 2 and 3).  The stateful modes need sgd_hp, sgd_step ({steps taken, arrival ticket})
-// and their state: hipErrorInvalidValue otherwise.
-// cnn_opt_fused: the same stateful updates (mode: 0 SGD + momentum / weight decay, 1 Adam, 2 AdamW) and the
-// fragment refresh as ONE launch after an all-reduce that ran outside the reduction kernel.
-hipError_t cnn_opt_fused(float* params, const float* grads, float* m, float* v, const float* hp, void* frag,
-                         int* step, int mode, hipStream_t s);
-// params -= lr * gscale * grads (plain SGD) and the matching fragment-image refresh, one launch (used
-// after the gradient all-reduce when world > 1).
+
+// The optimiser update the CNN kernels can apply to the flat parameters -- the optimiser's own update function
+// (optim_device.h) -- together with the refresh of the fragment slots of the weights it writes.  ONE numbering,
+// here, in the bindings and in Python (models/cnn_fused.py fused_update_mode()).
+enum CnnUpdateMode : int {
+  CNN_SGD = 0,        // plain SGD: w -= hp[HP_LR] * hp[HP_GRAD_SCALE] * g; no state
+  CNN_SGD_STATE = 1,  // SGD with momentum and / or L2 weight decay (m: momentum_buffer)
+  CNN_ADAM = 2,       // Adam, L2 weight decay (m: exp_avg, v: exp_avg_sq)
+  CNN_ADAMW = 3,      // AdamW
+};
+struct CnnUpdate {
+  int mode;         // CnnUpdateMode
+  const float* hp;  // float[HP_COUNT]; nullptr: no update
+  int* step;        // the optimiser's {steps taken, arrival ticket}, advanced on device; plain SGD: optional, [0] += 1
+  float* m;         // modes 1..3: flat fp32 state indexed like params
+  float* v;         // modes 2, 3
+};
+// The one home of the rules: the mode is 0..3; a stateful mode (1..3) needs hp, step and m; Adam and AdamW need v.
+// The launchers return hipErrorInvalidValue where it fails.
+bool cnn_update_valid(const CnnUpdate& u);
+
+// One training step, up to three launches on s:
+//   k_cnn_prep    when prep != 0: the fragment image from params (skipped while the image is current -- the
+//                 previous step's update wrote it);
+//   k_cnn_train   nwg workgroups: per-workgroup gradient slabs, loss partials, the fc1 activation image;
+//   k_cnn_reduce  the deterministic slab reduction into grads (16-B aligned; += when accumulate), which also
+//                 finalises the loss and advances the dropout counter.  With xv (an XgmiAllreduce's view, size > 1)
+//                 it first exchanges each workgroup's gradient chunk with every peer over xGMI and sums all ranks'
+//                 chunks in rank order (x xscale): grads receives the all-reduced gradient at no extra launch (no
+//                 accumulate then).  With update.hp != nullptr it applies `update` to the final gradient and
+//                 refreshes the fragment image, so the next step needs no prep.
+// After an all-reduce that ran outside the reduction kernel, cnn_opt_fused below is the update as one launch.
+struct CnnTrainArgs {
+  const float* images;  // [B, 1, 28, 28]
+  const int64_t* tgt;   // [B]
+  int B;
+  float* params;
+  void* frag;
+  unsigned long long* rng;  // the dropout counter
+  float *slabs, *loss_part;
+  uint16_t* acts;
+  int nwg;
+  float *loss, *grads;
+  float p_drop2, p_drop1;
+  int training, accumulate, prep;
+  unsigned long long* stamps;  // diagnostic, optional [nwg][16]: wall clock at each phase boundary
+  int stop_after;              // diagnostic: end the training kernel after phase stamp k (-1: run it all)
+  CnnUpdate update;
+  const XgmiView* xv;  // nullptr or size 1: no exchange
+  float xscale;
+};
+hipError_t cnn_train_fused(const CnnTrainArgs& a, hipStream_t s);
+// `u` on the all-reduced grads plus the fragment refresh, ONE launch: k_cnn_sgd for plain SGD (u.step may be
+// nullptr), k_cnn_opt<MODE> (optdev's numbering, converted in the launcher) for the stateful modes.  u.hp must be
+// set and frag 16-B aligned.
+hipError_t cnn_opt_fused(float* params, const float* grads, void* frag, const CnnUpdate& u, hipStream_t s);
 // 1 when the single-process fused tail's grid barrier timed out (PDE_CNN_FUSED_TAIL); reset clears it
 int cnn_tail_error(int reset);
-hipError_t cnn_sgd_fused(float* params, const float* grads, const float* hp, void* frag, hipStream_t s,
-                         int* step = nullptr);  // step: the optimiser's device step counter (+1 per call)
 // Forward-only evaluation of Net (eval mode: no dropout) on the training kernel's operands and precision: one
 // launch (two with prep = 1, which rebuilds the fragment image first), every activation in LDS.  Any B >= 1.
 // Each output is optional (nullptr skips it): logp [B,10] fp32 log-probabilities; pred [B] int64 argmax (the

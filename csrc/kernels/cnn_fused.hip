@@ -1423,7 +1423,7 @@ __device__ __forceinline__ void sgd_update(float* params, float lr, float gsc, u
 // indexed like params and owned by the threads that own the weight.  These modes need the 1-based step: every
 // block reads step[0] + 1 at role entry (one thread, a shared word, published by the role's own barrier) and
 // arrives at the ticket in step[1] at its end; the last of gridDim.x arrivals stores the new count and clears the
-// ticket (k_cnn_adamw's protocol), so no block can read a count another block already advanced.
+// ticket (k_cnn_opt's protocol), so no block can read a count another block already advanced.
 template <int OPT>
 __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s_epoch, int* s_fail,
                                                 const float* __restrict__ slabs, int nwg,
@@ -2003,26 +2003,29 @@ int cnn_slab_floats() { return NSLABP; }  // per workgroup, padded (SLAB_OFS)
 int cnn_act_rows() { return NACT; }
 int cnn_act_pitch(int nwg) { return act_pitch(nwg); }
 
-hipError_t cnn_train_fused(const float* images, const int64_t* tgt, int B, float* params, void* frag,
-                           unsigned long long* rng, float p_drop2, float p_drop1, int training, float* slabs,
-                           float* loss_part, uint16_t* acts, int nwg, float* loss, float* grads, const float* gscale,
-                           int accumulate, hipStream_t s, unsigned long long* stamps, int prep,
-                           const float* sgd_hp, int stop_after, int* sgd_step, const XgmiView* xv,
-                           float xscale, int opt_mode, float* opt_m, float* opt_v) {
-  if (reinterpret_cast<uintptr_t>(grads) & 15) return hipErrorInvalidValue;  // float4 gradient stores
-  // a stateful update (cnn_reduce_role's OPT) needs its hyper-parameters, the step words and its state
-  if (opt_mode < 0 || opt_mode > 3) return hipErrorInvalidValue;
-  if (opt_mode != 0 && (sgd_hp == nullptr || sgd_step == nullptr || opt_m == nullptr ||
-                        (opt_mode >= 2 && opt_v == nullptr)))
-    return hipErrorInvalidValue;
+bool cnn_update_valid(const CnnUpdate& u) {
+  if (u.mode < CNN_SGD || u.mode > CNN_ADAMW) return false;
+  if (u.mode == CNN_SGD) return true;
+  return u.hp != nullptr && u.step != nullptr && u.m != nullptr && (u.mode < CNN_ADAM || u.v != nullptr);
+}
+
+hipError_t cnn_train_fused(const CnnTrainArgs& a, hipStream_t s) {
+  const CnnUpdate& u = a.update;
+  const int nwg = a.nwg;
+  // The kernels still take a device pointer to a gradient scale (k_cnn_reduce's gscale, CnnTail::gscale) that no
+  // caller ever set: the launcher passes nullptr.  Taking the parameter out changes the kernels, so it is a change
+  // of its own, with a benchmark.
+  const float* const gscale = nullptr;
+  if (reinterpret_cast<uintptr_t>(a.grads) & 15) return hipErrorInvalidValue;  // float4 gradient stores
+  if (!cnn_update_valid(u)) return hipErrorInvalidValue;
   XgmiView view{};
   view.size = 1;
-  if (xv != nullptr && xv->size > 1) {
+  if (a.xv != nullptr && a.xv->size > 1) {
     // the exchange replaces the all-reduce of the gradients: no local accumulation in between, one flag
     // row and one staging float per parameter for each of this kernel's workgroups
-    if (accumulate || xv->blocks < RED_BLOCKS || xv->slot_bytes < static_cast<int64_t>(NPARAM) * 4)
+    if (a.accumulate || a.xv->blocks < RED_BLOCKS || a.xv->slot_bytes < static_cast<int64_t>(NPARAM) * 4)
       return hipErrorInvalidValue;
-    view = *xv;
+    view = *a.xv;
   }
   const size_t sm = sizeof(CnnSmem);
   // PDE_CNN_STORE: store flavour of the slabs / activations (out_st).  Write-through (2) is the default: the
@@ -2047,43 +2050,44 @@ hipError_t cnn_train_fused(const float* images, const int64_t* tgt, int B, float
                               static_cast<int>(sm));
     attr[breg ? 1 : 0][si] = true;
   }
-  if (reinterpret_cast<uintptr_t>(frag) & 15) return hipErrorInvalidValue;
-  if (prep)
-    hipLaunchKernelGGL(k_cnn_prep, dim3(ceil_div(NFRAG, 256)), dim3(256), 0, s, params, static_cast<u16x8*>(frag));
-  if (reinterpret_cast<uintptr_t>(acts) & 15) return hipErrorInvalidValue;
+  if (reinterpret_cast<uintptr_t>(a.frag) & 15) return hipErrorInvalidValue;
+  if (a.prep)
+    hipLaunchKernelGGL(k_cnn_prep, dim3(ceil_div(NFRAG, 256)), dim3(256), 0, s, a.params,
+                       static_cast<u16x8*>(a.frag));
+  if (reinterpret_cast<uintptr_t>(a.acts) & 15) return hipErrorInvalidValue;
   CnnTail tail{};
   unsigned* bar = nullptr;
   int* berr = nullptr;
   // (the stateful updates always take the two-launch form: the tail is instantiated for plain SGD only)
-  if (opt_mode == 0 && view.size == 1 && stamps == nullptr && stop_after < 0 && cnn_fused_tail_enabled() &&
-      nwg >= RED_BLOCKS &&
-      nwg <= cnn_device_cus() && cnn_barrier_words(s, &bar, &berr)) {
-    tail.gscale = gscale; tail.grads = grads; tail.loss = loss; tail.rng = rng; tail.params = params;
-    tail.hp = sgd_hp; tail.frag = static_cast<uint16_t*>(frag); tail.step = sgd_step; tail.bar = bar;
-    tail.err = berr; tail.accumulate = accumulate; tail.B = B; tail.on = 1;
+  if (u.mode == CNN_SGD && view.size == 1 && a.stamps == nullptr && a.stop_after < 0 && cnn_fused_tail_enabled() &&
+      nwg >= RED_BLOCKS && nwg <= cnn_device_cus() && cnn_barrier_words(s, &bar, &berr)) {
+    tail.gscale = gscale; tail.grads = a.grads; tail.loss = a.loss; tail.rng = a.rng; tail.params = a.params;
+    tail.hp = u.hp; tail.frag = static_cast<uint16_t*>(a.frag); tail.step = u.step; tail.bar = bar;
+    tail.err = berr; tail.accumulate = a.accumulate; tail.B = a.B; tail.on = 1;
   }
   // PDE_CNN_DIAG (timing diagnostics only, results invalid): 1 no reduce launch, 2 no train launch, 4 reduce
   // slab-column roles only, 8 reduce fc1-tile roles only, 16 no SGD update / fragment refresh in the reduce
   static const int diag = std::getenv("PDE_CNN_DIAG") ? std::atoi(std::getenv("PDE_CNN_DIAG")) : 0;
   if (!(diag & 2))
-    hipLaunchKernelGGL(train, dim3(nwg), dim3(T), sm, s, images, tgt, B, params,
-                       static_cast<const u16x8*>(frag), rng, p_drop2, p_drop1, training, slabs, loss_part, acts,
-                       stamps, stop_after, tail, xmap);
+    hipLaunchKernelGGL(train, dim3(nwg), dim3(T), sm, s, a.images, a.tgt, a.B, a.params,
+                       static_cast<const u16x8*>(a.frag), a.rng, a.p_drop2, a.p_drop1, a.training, a.slabs,
+                       a.loss_part, a.acts, a.stamps, a.stop_after, tail, xmap);
   if (!tail.on && !(diag & 1)) {
     const int rb0 = (diag & 8) ? RED_SLAB_BLOCKS : 0;
     const int nrb = (diag & 4) ? RED_SLAB_BLOCKS : (diag & 8) ? RED_BLOCKS - RED_SLAB_BLOCKS : RED_BLOCKS;
-    const float* hp = (diag & 16) ? nullptr : sgd_hp;
-    uint16_t* fr = static_cast<uint16_t*>(frag);
-    if (opt_mode == 0) {
-      hipLaunchKernelGGL(k_cnn_reduce<0>, dim3(nrb), dim3(RED_T), 0, s, slabs, nwg, acts, gscale, grads,
-                         accumulate, loss_part, B, loss, rng, params, hp, fr, sgd_step, view, xscale, rb0);
+    const float* hp = (diag & 16) ? nullptr : u.hp;
+    uint16_t* fr = static_cast<uint16_t*>(a.frag);
+    if (u.mode == CNN_SGD) {  // (no state arguments: k_cnn_reduce<0>'s pack is empty)
+      hipLaunchKernelGGL(k_cnn_reduce<0>, dim3(nrb), dim3(RED_T), 0, s, a.slabs, nwg, a.acts, gscale, a.grads,
+                         a.accumulate, a.loss_part, a.B, a.loss, a.rng, a.params, hp, fr, u.step, view, a.xscale,
+                         rb0);
     } else {
       using ReduceFn = decltype(&k_cnn_reduce<1, float*, float*>);
       static const ReduceFn kReduce[3] = {&k_cnn_reduce<1, float*, float*>, &k_cnn_reduce<2, float*, float*>,
                                           &k_cnn_reduce<3, float*, float*>};
-      hipLaunchKernelGGL(kReduce[opt_mode - 1], dim3(nrb), dim3(RED_T), 0, s, slabs, nwg, acts, gscale, grads,
-                         accumulate, loss_part, B, loss, rng, params, hp, fr, sgd_step, view, xscale, rb0, opt_m,
-                         opt_v);
+      hipLaunchKernelGGL(kReduce[u.mode - CNN_SGD_STATE], dim3(nrb), dim3(RED_T), 0, s, a.slabs, nwg, a.acts, gscale,
+                         a.grads, a.accumulate, a.loss_part, a.B, a.loss, a.rng, a.params, hp, fr, u.step, view,
+                         a.xscale, rb0, u.m, u.v);
     }
   }
   return hipGetLastError();
@@ -2110,27 +2114,21 @@ hipError_t cnn_eval_fused(const float* images, const int64_t* tgt, int B, const 
   return hipGetLastError();
 }
 
-hipError_t cnn_sgd_fused(float* params, const float* grads, const float* hp, void* frag, hipStream_t s, int* step) {
-  if (reinterpret_cast<uintptr_t>(frag) & 15) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_cnn_sgd, dim3(ceil_div(NPARAM, 256)), dim3(256), 0, s, params, grads, hp,
-                     static_cast<uint16_t*>(frag), step);
-  return hipGetLastError();
-}
-
-// AdamW (torch.optim.AdamW: the Horovod-elastic script's optimiser, horovod_mnist_elastic.py:41) on the flat
-// parameters, its exp_avg / exp_avg_sq as flat buffers, with the fragment image refreshed in the same pass -- the
-// multi-tensor update launch and the next step's fragment prep launch become ONE launch.  hp / step: the fused
-// optimiser's device hyper-parameters and {steps taken, arrival counter}, read and advanced exactly as its own
-// update kernel does (optim_device.h run_chunks), so its state_dict and later steps stay consistent.
+// The stateful updates (torch.optim's SGD with momentum / weight decay, Adam, AdamW -- the last is the Horovod-elastic
+// script's optimiser, horovod_mnist_elastic.py:41) on the flat parameters, their state as flat buffers, with the
+// fragment image refreshed in the same pass -- the multi-tensor update launch and the next step's fragment prep
+// launch become ONE launch.  hp / step: the fused optimiser's device hyper-parameters and {steps taken, arrival
+// counter}, read and advanced exactly as its own update kernel does (optim_device.h run_chunks), so its state_dict
+// and later steps stay consistent.
 //
 // MODE: optdev's (0 SGD with momentum and / or L2 weight decay -- m: the momentum buffers, v unused; 1 Adam with
-// L2; 2 AdamW).  The stateful updates after an all-reduce that did not run inside the slab reduction (RCCL, the
-// fusion engine, DDP); plain SGD keeps k_cnn_sgd.
+// L2; 2 AdamW), one less than the CnnUpdateMode.  The updates after an all-reduce that did not run inside the slab
+// reduction (RCCL, the fusion engine, DDP); plain SGD keeps k_cnn_sgd.
 template <int MODE>
-__global__ __launch_bounds__(256) void k_cnn_adamw(float* __restrict__ params, const float* __restrict__ grads,
-                                                   float* __restrict__ m, float* __restrict__ v,
-                                                   const float* __restrict__ hp, int* __restrict__ step,
-                                                   uint16_t* __restrict__ frag) {
+__global__ __launch_bounds__(256) void k_cnn_opt(float* __restrict__ params, const float* __restrict__ grads,
+                                                 float* __restrict__ m, float* __restrict__ v,
+                                                 const float* __restrict__ hp, int* __restrict__ step,
+                                                 uint16_t* __restrict__ frag) {
   __shared__ int s_step;
   if (threadIdx.x == 0) s_step = step[0] + 1;
   __syncthreads();
@@ -2155,21 +2153,20 @@ __global__ __launch_bounds__(256) void k_cnn_adamw(float* __restrict__ params, c
   }
 }
 
-// mode: optdev's MODE (0 SGD with momentum / weight decay, 1 Adam, 2 AdamW); v may be nullptr for mode 0
-hipError_t cnn_opt_fused(float* params, const float* grads, float* m, float* v, const float* hp, void* frag,
-                         int* step, int mode, hipStream_t s) {
-  if (mode < 0 || mode > 2 || m == nullptr || step == nullptr || (mode != 0 && v == nullptr))
+hipError_t cnn_opt_fused(float* params, const float* grads, void* frag, const CnnUpdate& u, hipStream_t s) {
+  if (!cnn_update_valid(u) || u.hp == nullptr || (reinterpret_cast<uintptr_t>(frag) & 15))
     return hipErrorInvalidValue;
-  using OptFn = decltype(&k_cnn_adamw<2>);
-  static const OptFn kOpt[3] = {&k_cnn_adamw<0>, &k_cnn_adamw<1>, &k_cnn_adamw<2>};
-  hipLaunchKernelGGL(kOpt[mode], dim3(ceil_div(NPARAM, 256)), dim3(256), 0, s, params, grads, m, v, hp, step,
-                     static_cast<uint16_t*>(frag));
+  uint16_t* fr = static_cast<uint16_t*>(frag);
+  if (u.mode == CNN_SGD) {
+    hipLaunchKernelGGL(k_cnn_sgd, dim3(ceil_div(NPARAM, 256)), dim3(256), 0, s, params, grads, u.hp, fr, u.step);
+  } else {
+    using OptFn = decltype(&k_cnn_opt<2>);
+    // the one place the CnnUpdateMode becomes optdev's MODE
+    static const OptFn kOpt[3] = {&k_cnn_opt<0>, &k_cnn_opt<1>, &k_cnn_opt<2>};
+    hipLaunchKernelGGL(kOpt[u.mode - CNN_SGD_STATE], dim3(ceil_div(NPARAM, 256)), dim3(256), 0, s, params, grads,
+                       u.m, u.v, u.hp, u.step, fr);
+  }
   return hipGetLastError();
-}
-
-hipError_t cnn_adamw_fused(float* params, const float* grads, float* m, float* v, const float* hp, void* frag,
-                           int* step, hipStream_t s) {
-  return cnn_opt_fused(params, grads, m, v, hp, frag, step, 2, s);
 }
 
 }  // namespace pde

@@ -186,14 +186,14 @@ class Trainer:
 
     def _fused_cnn_step(self, source, targets):
         xgmi = getattr(self.ddp.comm, "xgmi", None)
-        if self.ddp.world == 1:  # SGD (+ momentum / weight decay) + fragment refresh inside the slab reduction
-            return self.fused.forward_backward(source, targets, grad_out=self.ddp.flat_grad, sgd=self.optimizer)
-        if xgmi is not None:  # + the gradient all-reduce, exchanged over xGMI inside that kernel
+        if self.ddp.world == 1 or xgmi is not None:
+            # SGD (+ momentum / weight decay) + fragment refresh inside the slab reduction, which at world > 1 also
+            # exchanges the gradients over xGMI (an xgmi of size 1 is ignored)
             return self.fused.forward_backward(source, targets, grad_out=self.ddp.flat_grad, sgd=self.optimizer,
                                                xgmi=xgmi)
         loss = self.fused.forward_backward(source, targets, grad_out=self.ddp.flat_grad)
         self.ddp.sync_gradients()
-        self.fused.sgd_step(self.optimizer, self.ddp.flat_grad)
+        self.fused.opt_step(self.optimizer, self.ddp.flat_grad)
         return loss
 
     def _run_batch(self, source, targets):

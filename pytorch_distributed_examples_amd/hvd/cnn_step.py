@@ -28,20 +28,17 @@ class FusedHvdStep:
         self.model, self.opt, self.batch = model, optimizer, int(batch)
         self.fused = FusedCNN(model)
         from ..models.cnn_fused import fused_update_mode, opt_in_reduce_enabled
-        from ..ops.optim import FusedSGD
 
-        # a one-group FusedSGD (the DP script, mnist_horovod.py:50; any momentum / weight decay): the update rides in
-        # the fused kernel's slab reduction at world 1, else ONE launch after the engine's synchronize that also
-        # refreshes the bf16 fragment image -- the bench's hvd_cnn step.  A one-group FusedAdamW (the elastic script)
-        # or FusedAdam: update + fragment refresh in ONE launch (FusedCNN.opt_step); at world 1 inside the slab
-        # reduction too (PDE_CNN_OPT_IN_REDUCE=0 keeps the launch of its own).  Anything else: the wrapped
-        # optimiser's own step, fragments rebuilt in-kernel.
+        # a one-group FusedSGD (the DP script, mnist_horovod.py:50; any momentum / weight decay), FusedAdamW (the
+        # elastic script) or FusedAdam: the update rides in the fused kernel's slab reduction at world 1, else it is
+        # ONE launch after the engine's synchronize that also refreshes the bf16 fragment image (FusedCNN.opt_step)
+        # -- the bench's hvd_cnn step.  PDE_CNN_OPT_IN_REDUCE=0 keeps Adam / AdamW on the launch of their own at
+        # world 1 too.  Anything else: the wrapped optimiser's own step, fragments rebuilt in-kernel.
         self.mode = fused_update_mode(optimizer)
-        self.sgd_fast = self.mode is not None and isinstance(optimizer, FusedSGD)
-        self.adamw_fast = self.mode is not None and not self.sgd_fast
-        self.adam_in_reduce = self.adamw_fast and opt_in_reduce_enabled()
-        self.fused.always_prep = not (self.sgd_fast or self.adamw_fast)
-        if not self.sgd_fast:
+        sgd = self.mode in (0, 1)
+        self.in_reduce = sgd or (self.mode is not None and opt_in_reduce_enabled())
+        self.fused.always_prep = self.mode is None
+        if not sgd:
             from ..ops import functional as OF
 
             # the kernel rebuilds its fragment image from the fp32 weights every step: the optimiser need not keep
@@ -56,30 +53,19 @@ class FusedHvdStep:
         self.replays = 0
 
     def _eager(self, x, y):
-        if self.sgd_fast:
-            from . import core
-
-            if core.size() == 1:  # all-reduce = identity: SGD inside the reduction kernel
-                self.opt.synchronize()
-                return self.fused.forward_backward(x, y, grad_out=self.grads, sgd=self.opt)
+        if self.mode is None:
             loss = self.fused.forward_backward(x, y, grad_out=self.grads)
-            self.opt.synchronize()  # the engine (graph mode: stream-ordered on this stream)
-            with self.opt.skip_synchronize():
-                self.fused.sgd_step(self.opt, self.grads)
+            self.opt.step()
             return loss
-        if self.adam_in_reduce:
-            from . import core
+        from . import core
 
-            if core.size() == 1:  # all-reduce = identity: Adam / AdamW inside the reduction kernel
-                self.opt.synchronize()
-                return self.fused.forward_backward(x, y, grad_out=self.grads, opt=self.opt)
+        if self.in_reduce and core.size() == 1:  # all-reduce = identity: the update inside the reduction kernel
+            self.opt.synchronize()
+            return self.fused.forward_backward(x, y, grad_out=self.grads, opt=self.opt)
         loss = self.fused.forward_backward(x, y, grad_out=self.grads)
-        if self.adamw_fast:
-            self.opt.synchronize()  # the engine (graph mode: stream-ordered on this stream)
-            with self.opt.skip_synchronize():
-                self.fused.opt_step(self.opt, self.grads)
-            return loss
-        self.opt.step()
+        self.opt.synchronize()  # the engine (graph mode: stream-ordered on this stream)
+        with self.opt.skip_synchronize():
+            self.fused.opt_step(self.opt, self.grads)
         return loss
 
     def eager_step(self, x, y):

@@ -16,9 +16,11 @@ conv2's output and dropout(p=0.5) on fc1's (fresh masks every call; dropout disa
 
 Fused optimiser step: the training kernel reads the conv weights as a bf16 MFMA fragment image that a prep
 kernel writes from the fp32 parameters.  With ``sgd=opt`` (or ``opt=opt``) the slab reduction also applies the
-optimiser update and rewrites the fragment slots of the weights it updates; with :meth:`opt_step`
-(:meth:`sgd_step` / :meth:`adam_step` / :meth:`adamw_step`, after the gradient all-reduce) one kernel does the
-same.  Either way the next step skips the prep launch.  ``opt`` is a one-group ``FusedSGD`` (plain -- the
+optimiser update and rewrites the fragment slots of the weights it updates; :meth:`opt_step`, after a gradient
+all-reduce that ran elsewhere, is the same update as one launch (:meth:`sgd_step` / :meth:`adam_step` /
+:meth:`adamw_step` are :meth:`opt_step` behind a check of the optimiser's type).  Either way the next step skips
+the prep launch.  Both go through one update descriptor of the native layer (``CnnUpdate``: mode, hyper-parameters,
+step words, state) with one mode numbering.  ``opt`` is a one-group ``FusedSGD`` (plain -- the
 reference's ``optim.SGD(lr=0.01)``, mnist_horovod.py:50 -- or with momentum and / or weight decay),
 ``FusedAdam`` or ``FusedAdamW`` (:func:`fused_update_mode`); the stateful ones keep ``momentum_buffer`` /
 ``exp_avg`` / ``exp_avg_sq`` as views of flat buffers, so ``state_dict()`` and ``opt.step()`` see the same state::
@@ -27,7 +29,7 @@ reference's ``optim.SGD(lr=0.01)``, mnist_horovod.py:50 -- or with momentum and 
     loss = fused.forward_backward(x, y, grad_out=buf, sgd=opt)          # world 1: 2 launches per step
     loss = fused.forward_backward(x, y, grad_out=g, sgd=opt, xgmi=xa)   # world > 1 on one node: 2 launches
     loss = fused.forward_backward(x, y, grad_out=ddp.flat_grad)         # world > 1, any data plane:
-    ddp.sync_gradients(); fused.sgd_step(opt, ddp.flat_grad)            #   3 launches + all-reduce
+    ddp.sync_gradients(); fused.opt_step(opt, ddp.flat_grad)            #   3 launches + all-reduce
     loss = fused.forward_backward(x, y, opt=adamw)                      # a FusedAdamW: AdamW in the reduction
 
 With ``xgmi`` (a :class:`..parallel.xgmi_allreduce.XgmiAllreduce` over the data-parallel ranks) the slab
@@ -120,8 +122,9 @@ class FusedCNN:
             off += k
 
     def _update_args(self, opt):
-        """``(mode, device state, params)`` of an optimiser the fused update can apply (:func:`fused_update_mode`):
-        its state bound to the flat buffers BEFORE the optimiser builds its device table, so both see one state."""
+        """``(mode, device state, params, m, v)`` of an optimiser the fused update can apply
+        (:func:`fused_update_mode`): its state bound to the flat buffers BEFORE the optimiser builds its device table,
+        so both see one state; ``m`` / ``v``: the flat state buffers the mode uses, else ``None``."""
         mode = fused_update_mode(opt)
         assert mode is not None, "fused update needs a one-group FusedSGD, FusedAdam or FusedAdamW"
         self._bind_state(opt, mode)
@@ -130,7 +133,7 @@ class FusedCNN:
         st = opt._group_dev(0, group, params)
         for p in params:  # the fused update writes the fp32 weights only (plus its own fragment image)
             OF.release_compute_copies(p)
-        return mode, st, params
+        return mode, st, params, (self._opt_m if mode >= 1 else None), (self._opt_v if mode >= 2 else None)
 
     def _after_update(self, opt, params):
         # the step count lives in the optimizer's device counter (advanced by the fused kernels, so hipGraph
@@ -141,16 +144,11 @@ class FusedCNN:
     @torch.no_grad()
     def opt_step(self, opt, grads: torch.Tensor):
         """``opt.step()`` for the flat parameters fused with the fragment-image refresh, ONE launch: plain SGD
-        (``k_cnn_sgd``), SGD with momentum / weight decay, Adam or AdamW (``k_cnn_adamw<MODE>``) -- the update after
+        (``k_cnn_sgd``), SGD with momentum / weight decay, Adam or AdamW (``k_cnn_opt<MODE>``) -- the update after
         a gradient all-reduce that ran outside the reduction kernel.  The update math and the device step counter are
         the optimiser's own (optim_device.h)."""
-        mode, st, params = self._update_args(opt)
-        C = _native.C()
-        if mode == 0:
-            C.cnn_sgd(self.flat, grads, st["hp"], self.frag, st["step"])
-        else:
-            C.cnn_opt(self.flat, grads, self._opt_m, self._opt_v if mode >= 2 else None, st["hp"], self.frag,
-                      st["step"], mode - 1)
+        mode, st, params, m, v = self._update_args(opt)
+        _native.C().cnn_opt(self.flat, grads, self.frag, st["hp"], st["step"], mode=mode, m=m, v=v)
         self._after_update(opt, params)
 
     def sgd_step(self, opt, grads: torch.Tensor):
@@ -167,16 +165,13 @@ class FusedCNN:
         assert isinstance(opt, FusedAdam), "adam_step needs a FusedAdam"
         self.opt_step(opt, grads)
 
-    @torch.no_grad()
     def adamw_step(self, opt, grads: torch.Tensor):
-        """``opt.step()`` of a one-group FusedAdamW over the flat parameters fused with the fragment-image refresh:
-        ONE launch (``k_cnn_adamw``) instead of the multi-tensor update plus the next step's prep launch."""
+        """:meth:`opt_step` of a one-group FusedAdamW: one launch instead of the multi-tensor update plus the next
+        step's prep launch."""
         from ..ops.optim import FusedAdamW
 
-        assert isinstance(opt, FusedAdamW) and len(opt.param_groups) == 1, "adamw_step needs one FusedAdamW group"
-        _, st, params = self._update_args(opt)
-        _native.C().cnn_adamw(self.flat, grads, self._opt_m, self._opt_v, st["hp"], self.frag, st["step"])
-        self._after_update(opt, params)
+        assert isinstance(opt, FusedAdamW), "adamw_step needs a FusedAdamW"
+        self.opt_step(opt, grads)
 
     def _nwg(self, B: int) -> int:
         if self.workgroups:
@@ -214,18 +209,16 @@ class FusedCNN:
         y = y.long().contiguous()
         training = self.net.training
         prep = self.always_prep or self._frag_gen is None or self._frag_gen != OF.weight_generation()
-        mode, hp, step, params, om, ov = 0, None, None, None, None, None
+        update = {}
         if opt is not None:
-            mode, st, params = self._update_args(opt)
-            hp, step = st["hp"], st["step"]
-            if mode != 0:
-                om, ov = self._opt_m, (self._opt_v if mode >= 2 else None)
+            mode, st, params, m, v = self._update_args(opt)
+            update = dict(hp=st["hp"], step=st["step"], mode=mode, m=m, v=v)
         view, xscale = None, 1.0
         if xgmi is not None and xgmi.size > 1:
             view, xscale = xgmi.view(), (1.0 / xgmi.size if avg else 1.0)
         loss = C.cnn_train(x, y, self.flat, OF._rng_counter(x.device), p_drop2, p_drop1, training, grad_out,
-                           accumulate, None, self.stamps, self.frag, prep, hp, self.stop_after, step, view, xscale,
-                           mode, om, ov)
+                           accumulate, stamps=self.stamps, frag=self.frag, prep=prep, stop_after=self.stop_after,
+                           xgmi_view=view, xscale=xscale, **update)
         if opt is not None:
             self._after_update(opt, params)
         else:

@@ -15,7 +15,7 @@ Variants:
   sgd_mom_generic    the same optimiser through forward_backward + opt.step(): train, reduce, the multi-tensor
                      update and the next step's fragment prep -- the only route before this one       4 launches
   adamw_reduce       AdamW inside the reduction                                                      2 launches
-  adamw_step         forward_backward + FusedCNN.adamw_step (k_cnn_adamw)                             3 launches
+  adamw_step         forward_backward + FusedCNN.adamw_step (k_cnn_opt<2>)                            3 launches
 
 Needs a GPU; one JSON row per (batch, variant) plus one verdict row per batch is appended to ``--out`` and printed.
 Exit status 1 when momentum inside the reduction measured slower than the generic route.

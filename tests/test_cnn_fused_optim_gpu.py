@@ -1,5 +1,5 @@
 """Momentum SGD, L2 weight decay, Adam and AdamW inside the fused CNN's slab reduction (cnn_reduce_role<OPT>) and
-in the one-launch update behind an all-reduce (k_cnn_adamw<MODE>): against the generic route (forward_backward +
+in the one-launch update behind an all-reduce (k_cnn_opt<MODE>): against the generic route (forward_backward +
 ``opt.step()``, a fragment prep every step), against ``torch.optim``, and for step counting, state binding, the
 fragment image and hipGraph replay.  Eval mode throughout (no dropout), so the routes can be compared.
 
@@ -161,8 +161,8 @@ def test_update_in_reduction_matches_generic_route_and_torch(gpu, case, B):
 
 @pytest.mark.parametrize("case", list(CASES))
 def test_post_allreduce_update_matches_generic_route_and_torch(gpu, case):
-    """sgd_step / adam_step / adamw_step (k_cnn_adamw<MODE>): the update after an all-reduce that ran outside the
-    reduction kernel, same two comparisons."""
+    """opt_step (k_cnn_sgd / k_cnn_opt<MODE>): the update after an all-reduce that ran outside the reduction kernel,
+    same two comparisons; sgd_step / adam_step / adamw_step reach the same launch and refuse the other optimisers."""
     from pytorch_distributed_examples_amd.models.cnn_fused import FusedCNN
 
     f, opt = _run_route(gpu, case, 6, "post")
@@ -171,7 +171,14 @@ def test_post_allreduce_update_matches_generic_route_and_torch(gpu, case):
     f2 = FusedCNN(net)
     g2 = f2.grad_buffer()
     opt2 = _make_opt(case, net.parameters())
-    step = {"sgd": f2.sgd_step, "adam": f2.adam_step, "adamw": f2.adamw_step}[CASES[case][0]]
+    named = {"sgd": f2.sgd_step, "adam": f2.adam_step, "adamw": f2.adamw_step}
+    step = named.pop(CASES[case][0])
+    before = f2.flat.detach().clone()
+    for other in named.values():  # the other optimisers' entry points refuse this one before any launch
+        with pytest.raises(AssertionError):
+            other(opt2, g2)
+    torch.cuda.synchronize()
+    assert torch.equal(f2.flat, before) and getattr(f2, "_opt_m", None) is None
     for x, y in _batches(gpu, 6):
         f2.forward_backward(x, y, grad_out=g2)
         step(opt2, g2)
@@ -296,7 +303,7 @@ def test_momentum_step_replays_in_a_hipgraph(gpu):
 
 
 def test_plain_sgd_keeps_mode_0_and_its_bits(gpu):
-    """momentum = 0 and weight_decay = 0 select opt_mode 0 -- today's kernel -- and three steps equal the generic
+    """momentum = 0 and weight_decay = 0 select mode 0 -- today's kernel -- and three steps equal the generic
     route bit for bit (the existing guarantee, through the new argument)."""
     from pytorch_distributed_examples_amd.models.cnn_fused import FusedCNN, fused_update_mode
     from pytorch_distributed_examples_amd.ops.optim import FusedSGD
@@ -349,21 +356,34 @@ def test_invalid_combinations_raise(gpu):
     rng = OF._rng_counter(gpu)
     m = torch.zeros_like(f.flat)
 
-    def train(mode, om, ov, hp=st["hp"], step=st["step"]):
-        return C.cnn_train(x, y, f.flat, rng, 0.5, 0.5, False, g, False, None, None, f.frag, True, hp, -1, step, None,
-                           1.0, mode, om, ov)
+    def train(mode, m, v, hp=st["hp"], step=st["step"]):
+        return C.cnn_train(x, y, f.flat, rng, 0.5, 0.5, False, g, False, frag=f.frag, prep=True, hp=hp, step=step,
+                           mode=mode, m=m, v=v)
 
-    with pytest.raises(RuntimeError, match="opt_m"):
+    with pytest.raises(RuntimeError, match="needs m "):
         train(1, None, None)
-    with pytest.raises(RuntimeError, match="opt_v"):
+    with pytest.raises(RuntimeError, match="need v "):
         train(3, m, None)
-    with pytest.raises(RuntimeError, match="sgd_hp and sgd_step"):
+    with pytest.raises(RuntimeError, match="needs hp and step"):
         train(1, m, None, step=None)
     with pytest.raises(RuntimeError, match="shaped like params"):
         train(1, m[:-4], None)
-    with pytest.raises(RuntimeError, match="opt_mode"):
+    with pytest.raises(RuntimeError, match="mode must be"):
         train(4, m, m)
-    with pytest.raises(RuntimeError):
-        C.cnn_opt(f.flat, g, m, None, st["hp"], f.frag, st["step"], 2)  # AdamW without exp_avg_sq
+
+    def update(mode, m, v, frag=f.frag):
+        return C.cnn_opt(f.flat, g, frag, st["hp"], st["step"], mode=mode, m=m, v=v)
+
+    with pytest.raises(RuntimeError, match="need v "):
+        update(3, m, None)  # AdamW without exp_avg_sq
+    # the refusals the one checker makes uniform
+    unaligned = torch.empty(f.frag.numel() + 16, dtype=torch.uint8, device=gpu)[1:]
+    assert unaligned.data_ptr() % 16 == 1 and unaligned.nbytes >= C.cnn_frag_bytes()
+    with pytest.raises(RuntimeError, match="frag must be a 16-B aligned"):
+        update(1, m, None, frag=unaligned)
+    with pytest.raises(RuntimeError, match="shaped like params"):
+        update(1, m.cpu(), None)
+    with pytest.raises(RuntimeError, match="mode must be"):
+        update(4, m, m)
     torch.cuda.synchronize()
     assert torch.equal(f.flat, before)  # nothing was launched

@@ -1,7 +1,7 @@
 """The stateful updates over the in-kernel xGMI gradient exchange, rehearsed on ONE GPU as in tests/test_xgmi_gpu.py:
 two processes share the card and map each other's IPC-exported staging buffers.  SGD with momentum + weight decay
 and AdamW inside the slab reduction (exchange, then update) against local gradients all-reduced over gloo plus the
-one-launch update (k_cnn_adamw<MODE>); weights and optimiser state bit-identical across the two ranks."""
+one-launch update (k_cnn_opt<MODE>); weights and optimiser state bit-identical across the two ranks."""
 import os
 import subprocess
 import sys

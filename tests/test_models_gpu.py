@@ -569,7 +569,7 @@ def test_fused_cnn_single_launch_tail_matches_two_launches(gpu, monkeypatch):
 
 
 def test_fused_cnn_adamw_step_matches_multi_tensor_adamw(gpu):
-    """FusedCNN.adamw_step (k_cnn_adamw: AdamW over the flat parameters + fragment refresh in ONE launch, the
+    """FusedCNN.adamw_step (k_cnn_opt<2>: AdamW over the flat parameters + fragment refresh in ONE launch, the
     Horovod-elastic step) against (a) an fp32 torch.optim.AdamW step on the same flat gradient, every step, and
     (b) the multi-tensor FusedAdamW launch + the fragment prep over several steps: same losses, weights and optimiser
     state to fp32 rounding (the two kernels inline the same update function; the compiler may contract its
@@ -595,10 +595,10 @@ def test_fused_cnn_adamw_step_matches_multi_tensor_adamw(gpu):
     for x, y in batches:  # the reference run first: its optimiser steps bump the global weight generation
         ref_losses.append(f_ref.forward_backward(x, y, grad_out=g_ref).clone())
         o_ref.step()
-    for i, (x, y) in enumerate(batches):  # then the fused run: its 2nd..4th steps reuse k_cnn_adamw's fragments
+    for i, (x, y) in enumerate(batches):  # then the fused run: its 2nd..4th steps reuse k_cnn_opt's fragments
         l_fus = f_fus.forward_backward(x, y, grad_out=g_fus)
         if i > 0:
-            assert f_fus._frag_gen == OF.weight_generation()  # no prep launch: the fragments come from k_cnn_adamw
+            assert f_fus._frag_gen == OF.weight_generation()  # no prep launch: the fragments come from k_cnn_opt
         with torch.no_grad():
             p_t.copy_(f_fus.flat)
         p_t.grad = g_fus.detach().clone()
