@@ -1475,6 +1475,34 @@ void cnn_opt(Tensor& params, const Tensor& grads, Tensor& frag, const Tensor& hp
         "cnn_opt");
 }
 
+// hvd.Adasum of the ranks' weight deltas behind a cnn_train without update or exchange (FusedCNN.adasum_step): the
+// local update of `mode` (state and step advance, params keep the starting weights), the delta exchange with its
+// Gram pass, then params += the combined delta with the fragment refresh -- TWO launches.  xgmi_view / gram /
+// gram_rows: XgmiAllreduce.view() and .gram_workspace() of a one-shot instance over a power-of-two world.
+void cnn_adasum_step(Tensor& params, const Tensor& grads, Tensor& frag, const Tensor& hp, const Tensor& step,
+                     int64_t mode, const optional<Tensor>& m, const optional<Tensor>& v,
+                     const std::vector<int64_t>& xgmi_view, int64_t gram, int64_t gram_rows) {
+  CHECK_IN(params); CHECK_IN(grads); CHECK_F32(params); CHECK_F32(grads);
+  TORCH_CHECK(params.numel() == pde::cnn_num_params() && grads.numel() == params.numel() &&
+                  grads.device() == params.device(),
+              "cnn_adasum_step: params and grads must be the flat Net parameters and their gradient, on one device");
+  check_cnn_frag(frag, "cnn_adasum_step");
+  const pde::CnnUpdate u = cnn_update_from(params, mode, hp, step, m, v, "cnn_adasum_step");
+  TORCH_CHECK(step.numel() >= 2, "cnn_adasum_step: step must be the optimiser's int32[2] {steps taken, ticket}");
+  const pde::XgmiView xv = xgmi_view_from(xgmi_view, "cnn_adasum_step");
+  TORCH_CHECK(xv.size >= 2 && xv.size <= pde::kXgmiMaxRanks && (xv.size & (xv.size - 1)) == 0,
+              "cnn_adasum_step: Adasum needs a power-of-two world of 2..8 ranks, not ", xv.size);
+  const int64_t wgs = (pde::cnn_num_params() + 255) / 256;
+  TORCH_CHECK(xv.blocks >= wgs, "cnn_adasum_step: the xGMI instance has ", xv.blocks, " flag rows, the step needs ", wgs);
+  TORCH_CHECK(gram != 0 && gram_rows >= wgs + 8, "cnn_adasum_step: the Gram workspace has ", gram_rows,
+              " rows, the step needs ", wgs + 8);
+  TORCH_CHECK(xv.slot_bytes >= static_cast<int64_t>(pde::cnn_num_params()) * 4,
+              "cnn_adasum_step: the xGMI staging slot does not hold the parameters");
+  check(pde::cnn_adasum_step(params.data_ptr<float>(), grads.data_ptr<float>(), frag.data_ptr(), u, xv,
+                             reinterpret_cast<double*>(gram), static_cast<int>(gram_rows), cur_stream()),
+        "cnn_adasum_step");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1486,6 +1514,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("v") = py::none());
   m.def("cnn_opt", &cnn_opt, py::arg("params"), py::arg("grads"), py::arg("frag"), py::arg("hp"), py::arg("step"),
         py::arg("mode"), py::arg("m") = py::none(), py::arg("v") = py::none());
+  m.def("cnn_adasum_step", &cnn_adasum_step, py::arg("params"), py::arg("grads"), py::arg("frag"), py::arg("hp"),
+        py::arg("step"), py::arg("mode"), py::arg("m") = py::none(), py::arg("v") = py::none(), py::kw_only(),
+        py::arg("xgmi_view"), py::arg("gram"), py::arg("gram_rows"));
   m.def("mlp_train_grid", &mlp_train_grid_py);
   m.def("mlp_train", &mlp_train, py::arg("x"), py::arg("y"), py::arg("w"), py::arg("b"), py::arg("gw"), py::arg("gb"),
         py::arg("mw"), py::arg("vw"), py::arg("mb"), py::arg("vb"), py::arg("wbf"), py::arg("wtbf"), py::arg("act"),

@@ -199,6 +199,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              w.push_back(reinterpret_cast<int64_t>(v.host));
              return w;
            })
+      // (device pointer, rows) of the Adasum Gram workspace, for kernels that fold the Adasum exchange in
+      .def("gram_workspace",
+           [](const XgmiAllreduce& x) {
+             return std::make_pair(reinterpret_cast<int64_t>(x.gram()), static_cast<int64_t>(x.gram_rows()));
+           })
       .def("set_read_delay_us", &XgmiAllreduce::set_read_delay_us)
       .def("error", [](XgmiAllreduce& x, bool sync) { py::gil_scoped_release nogil; return x.error(sync); },
            py::arg("sync") = true)

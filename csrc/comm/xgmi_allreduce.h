@@ -57,6 +57,11 @@ class XgmiAllreduce {
   // weights + combine), both hipGraph-capturable; the result is bit-identical on all ranks.
   void adasum(const float* src, float* dst, int64_t n, const std::vector<int64_t>& segs, float scale, hipStream_t s);
   XgmiView view() const;  // device view for kernels that fold the exchange in (xgmi_device.h)
+  // adasum's partial-Gram workspace for kernels that fold the Adasum exchange in (the fused CNN's delta / apply
+  // launches): gram_rows() rows of kXgmiGramRow doubles, device-local, allocated at construction (nullptr / 0 at
+  // world 1) -- a kernel writes row b + s for (workgroup b, segment s)
+  double* gram() const { return gram_; }
+  int gram_rows() const { return gram_ != nullptr ? blocks_ + kMaxAdasumSegs : 0; }
   // test hook: every workgroup of this rank stalls `us` microseconds between its flag wait and its peer reads
   void set_read_delay_us(double us) { read_delay_ticks_ = static_cast<uint64_t>(us * 100.0); }
   // 0, or 1 when some workgroup timed out waiting for a peer (or gave up on the host's abort word).

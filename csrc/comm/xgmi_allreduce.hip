@@ -302,6 +302,7 @@ __global__ void k_scale(const float* src, float* dst, int64_t n, float scale) {
 // workspace row b + s: consecutive pieces advance b, s or both, so the row is unique, rows of one segment are
 // contiguous, and the last one is < blocks + kMaxAdasumSegs.
 constexpr int kGramMax = kXgmiMaxRanks * (kXgmiMaxRanks + 1) / 2;  // workspace row: packed upper triangle, <= 36
+static_assert(kGramMax == kXgmiGramRow, "the row pitch kernels outside this file use (xgmi_view.h)");
 constexpr int kWaves = kThreads / 64;
 
 struct AdasumSegs {

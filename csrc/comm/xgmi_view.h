@@ -16,6 +16,8 @@ constexpr int kXgmiStateWords = 4;
 constexpr int kXgmiHostError = 0;  // 1 + epoch of the first timed-out wait (0: none); read by the host, no sync
 constexpr int kXgmiHostAbort = 1;  // the host sets it (elastic round changed, engine failed): spins give up
 constexpr int kXgmiHostWords = 16;
+// doubles per row of an XgmiAllreduce's Adasum Gram workspace: the packed upper triangle of an 8 x 8 Gram matrix
+constexpr int kXgmiGramRow = kXgmiMaxRanks * (kXgmiMaxRanks + 1) / 2;
 
 struct XgmiView {
   char* base[kXgmiMaxRanks];  // every rank's mapped [flags | slot0 | slot1] allocation (base[rank] = mine)

@@ -364,6 +364,20 @@ hipError_t cnn_train_fused(const CnnTrainArgs& a, hipStream_t s);
 // nullptr), k_cnn_opt<MODE> (optdev's numbering, converted in the launcher) for the stateful modes.  u.hp must be
 // set and frag 16-B aligned.
 hipError_t cnn_opt_fused(float* params, const float* grads, void* frag, const CnnUpdate& u, hipStream_t s);
+// hvd.Adasum of the ranks' weight DELTAS behind cnn_train_fused (no update, no exchange there: grads holds this
+// rank's local mean gradient), TWO launches on s, hipGraph-capturable:
+//   k_cnn_adasum_delta  `u` applied locally with the optimiser's own functions -- the state and the step words
+//                       advance, params keeps the shared starting weights --, the delta staged and exchanged over
+//                       xv's one-shot protocol, every (tensor, chunk) piece's fp64 Gram written to gram;
+//   k_cnn_adasum_apply  per tensor the Adasum weights from the summed Gram rows, params += sum_r w_r delta_r in rank
+//                       order (bit-identical on all ranks), fragment image refreshed.  A timed-out exchange (xv's
+//                       error word) leaves params as they were.
+// cnn_opt_fused's rules for u / frag, and u.step is required in every mode ({steps taken, arrival ticket}); xv: a
+// one-shot XgmiAllreduce's view of a power-of-two world of 2..8 ranks with at least one flag row per workgroup and
+// a slot that holds the parameters; gram / gram_rows: that instance's Gram workspace (XgmiAllreduce::gram()).
+// hipErrorInvalidValue where any of it fails.
+hipError_t cnn_adasum_step(float* params, const float* grads, void* frag, const CnnUpdate& u, const XgmiView& xv,
+                           double* gram, int gram_rows, hipStream_t s);
 // 1 when the single-process fused tail's grid barrier timed out (PDE_CNN_FUSED_TAIL); reset clears it
 int cnn_tail_error(int reset);
 // Forward-only evaluation of Net (eval mode: no dropout) on the training kernel's operands and precision: one

@@ -28,6 +28,7 @@
 #include <cstddef>
 #include <type_traits>
 
+#include "adasum_weights.h"
 #include "common.cuh"
 #include "optim_device.h"
 #include "pde_kernels.h"
@@ -2166,6 +2167,204 @@ hipError_t cnn_opt_fused(float* params, const float* grads, void* frag, const Cn
     hipLaunchKernelGGL(kOpt[u.mode - CNN_SGD_STATE], dim3(ceil_div(NPARAM, 256)), dim3(256), 0, s, params, grads,
                        u.m, u.v, u.hp, u.step, fr);
   }
+  return hipGetLastError();
+}
+
+// ---- hvd.Adasum of the weight DELTAS (hvd/optimizer.py _adasum_step), two launches behind forward_backward ----
+// Per rank r: delta_r = local_update(start, g_r, state_r) - start, and w = start + adasum_r(delta_r) with one set of
+// coefficients per parameter TENSOR (adasum_weights.h).  Both launches run k_cnn_opt's decomposition -- one parameter
+// per thread, ceil(NPARAM / 256) workgroups of 256, the same on every rank -- so a workgroup's 256-element chunk is
+// what it stages, what it reads from the peers and what it updates.  A PIECE is (tensor s) x (chunk b); its partial
+// Gram goes to workspace row b + s (k_xgmi_adasum_gram's numbering, xgmi_allreduce.hip: unique, the rows of one tensor
+// contiguous).  The Gram and combine arithmetic are that file's (fp64 sums of exact products in a fixed order, fp32
+// weights, rank-order fmas), written out again here for the one-element-per-thread layout: the stand-alone kernels
+// stay as they are.
+constexpr int ADA_T = 256, ADA_WAVES = ADA_T / 64, ADA_NSEG = 8;
+constexpr int ADA_BLOCKS = (NPARAM + ADA_T - 1) / ADA_T;
+struct CnnSegEnds {
+  int end[ADA_NSEG];  // cumulative element ends of Net's parameter tensors in the flat buffer
+};
+constexpr CnnSegEnds kCnnSegEnds = {{O_B1, O_W2, O_B2, O_FC1W, O_FC1B, O_FC2W, O_FC2B, NPARAM}};
+
+// Launch A.  MODE: the CnnUpdateMode; NR: the world size.  The local update with the optimiser's own functions
+// (sgd_update's expression / optdev::update), state stored, the weight NOT: params keeps `start` for launch B, so
+// no copy of the starting weights exists.  The delta is staged in this rank's slot, exchanged (xgmi_device.h), and
+// every piece's Gram over all ranks' slots is accumulated in fp64: per thread one element, wave shuffle, the
+// workgroup's waves in order -- no floating-point atomics, the same bits on every rank.  Then k_cnn_opt's step ticket.
+template <int MODE, int NR>
+__global__ __launch_bounds__(ADA_T) void k_cnn_adasum_delta(const float* __restrict__ params,
+                                                            const float* __restrict__ grads, float* __restrict__ m,
+                                                            float* __restrict__ v, const float* __restrict__ hp,
+                                                            int* __restrict__ step, XgmiView xv, CnnSegEnds segs,
+                                                            double* __restrict__ gram) {
+  constexpr int NG = NR * (NR + 1) / 2;
+  __shared__ uint32_t s_epoch;
+  __shared__ int s_fail;
+  __shared__ int s_step;
+  __shared__ double s_part[ADA_WAVES][NG];
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (tid == 0) s_step = step[0] + 1;
+  const uint32_t epoch = xgmi_epoch(xv, b, &s_epoch);  // (its barrier publishes s_step too)
+  const int p = b * ADA_T + tid;
+  const bool live = p < NPARAM;
+  if constexpr (MODE == CNN_SGD) {
+    if (live) {
+      const float w0 = params[p];
+      const float w1 = w0 - hp[HP_LR] * (grads[p] * hp[HP_GRAD_SCALE]);
+      xgmi_slot(xv, xv.rank, epoch)[p] = w1 - w0;
+    }
+  } else {
+    const optdev::Hyper h = optdev::load_hyper<MODE - 1>(hp, s_step);
+    if (live) {
+      const float w0 = params[p];
+      float w1 = w0, mm = m[p], vv = 0.f;
+      if constexpr (MODE >= CNN_ADAM) vv = v[p];
+      optdev::update<MODE - 1>(h, w1, grads[p], mm, vv);
+      m[p] = mm;
+      if constexpr (MODE >= CNN_ADAM) v[p] = vv;
+      xgmi_slot(xv, xv.rank, epoch)[p] = w1 - w0;
+    }
+  }
+  if (xgmi_publish_and_wait(xv, b, epoch, &s_fail)) {
+    xgmi_read_delay(xv);
+    float x[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) x[r] = live ? xgmi_slot(xv, r, epoch)[p] : 0.f;
+    const int lo = b * ADA_T;
+    const int hi = lo + ADA_T < NPARAM ? lo + ADA_T : NPARAM;
+    int s = 0;
+    while (s < ADA_NSEG - 1 && segs.end[s] <= lo) ++s;  // the first tensor that reaches into this chunk
+    for (int plo = lo; plo < hi && s < ADA_NSEG; ++s) {
+      const int phi = segs.end[s] < hi ? segs.end[s] : hi;
+      const bool in = p >= plo && p < phi;
+      double g[NG];
+      {
+        int k = 0;
+#pragma unroll
+        for (int i = 0; i < NR; ++i)
+#pragma unroll
+          for (int j = i; j < NR; ++j)
+            g[k++] = in ? static_cast<double>(x[i]) * static_cast<double>(x[j]) : 0.0;
+      }
+#pragma unroll
+      for (int k = 0; k < NG; ++k) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) g[k] += __shfl_down(g[k], off, 64);
+      }
+      if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < NG; ++k) s_part[tid >> 6][k] = g[k];
+      }
+      __syncthreads();
+      if (tid < NG) {
+        double t = s_part[0][tid];
+#pragma unroll
+        for (int w = 1; w < ADA_WAVES; ++w) t += s_part[w][tid];
+        gram[static_cast<int64_t>(b + s) * kXgmiGramRow + tid] = t;
+      }
+      __syncthreads();  // s_part is reused by the next piece
+      plo = phi;
+    }
+  }
+  xgmi_finish(xv, b, epoch);
+  // (every block read the old count before its arrival: the last one publishes -- k_cnn_opt's protocol)
+  if (tid == 0) {
+    const int prev = atomicAdd(step + 1, 1);
+    if (prev == static_cast<int>(gridDim.x) - 1) {
+      step[0] = s_step;
+      step[1] = 0;
+    }
+  }
+}
+
+// Launch B.  It re-reads the peers' slots of the call launch A exchanged: the two-slot lifetime argument above
+// k_xgmi_adasum_combine (xgmi_allreduce.hip) covers this second launch unchanged.  The epoch is the one launch A's
+// xgmi_finish stored; a set error word means some chunk's Gram or bytes are missing, and nothing is written.  Every
+// workgroup sums the partial rows of the tensors it touches in row order and derives the weights with the same code
+// from the same bits, on every rank; w = start + (w_0 x_0, then fmas in rank order), and the bf16 fragment slots of
+// the new weight are refreshed, so the next step needs no prep launch.
+template <int NR>
+__global__ __launch_bounds__(ADA_T) void k_cnn_adasum_apply(float* __restrict__ params, uint16_t* __restrict__ frag,
+                                                            XgmiView xv, CnnSegEnds segs,
+                                                            const double* __restrict__ gram) {
+  constexpr int NG = NR * (NR + 1) / 2;
+  __shared__ double s_G[NR * NR];
+  __shared__ double s_w[NR];
+  __shared__ float s_wf[NR];
+  __shared__ uint32_t s_state[2];
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (tid == 0) {  // one read per workgroup: every thread takes the same branch
+    s_state[0] = __hip_atomic_load(xv.state + kXgmiStateError, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_state[1] = __hip_atomic_load(xv.state + kXgmiStateEpoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (s_state[0] != 0u) return;
+  const uint32_t epoch = s_state[1];
+  const int p = b * ADA_T + tid;
+  const int lo = b * ADA_T;
+  const int hi = lo + ADA_T < NPARAM ? lo + ADA_T : NPARAM;
+  int s = 0;
+  while (s < ADA_NSEG - 1 && segs.end[s] <= lo) ++s;
+  for (int plo = lo; plo < hi && s < ADA_NSEG; ++s) {
+    const int phi = segs.end[s] < hi ? segs.end[s] : hi;
+    const int seg_lo = s == 0 ? 0 : segs.end[s - 1];
+    const int row0 = seg_lo / ADA_T + s, row1 = (segs.end[s] - 1) / ADA_T + s;
+    if (tid < NG) {
+      double t = gram[static_cast<int64_t>(row0) * kXgmiGramRow + tid];
+      for (int row = row0 + 1; row <= row1; ++row) t += gram[static_cast<int64_t>(row) * kXgmiGramRow + tid];
+      int i = 0, k = tid;  // packed upper-triangle index -> (i, j)
+      while (k >= NR - i) {
+        k -= NR - i;
+        ++i;
+      }
+      const int j = i + k;
+      s_G[i * NR + j] = t;
+      s_G[j * NR + i] = t;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      adasum_weights(s_G, NR, s_w);
+      for (int r = 0; r < NR; ++r) s_wf[r] = static_cast<float>(s_w[r]);
+    }
+    __syncthreads();
+    if (p >= plo && p < phi) {
+      float acc = s_wf[0] * xgmi_slot(xv, 0, epoch)[p];
+#pragma unroll
+      for (int r = 1; r < NR; ++r) acc = __fmaf_rn(s_wf[r], xgmi_slot(xv, r, epoch)[p], acc);
+      const float w = params[p] + acc;
+      params[p] = w;
+      write_frag(frag, p, w);
+    }
+    plo = phi;
+  }
+}
+
+hipError_t cnn_adasum_step(float* params, const float* grads, void* frag, const CnnUpdate& u, const XgmiView& xv,
+                           double* gram, int gram_rows, hipStream_t s) {
+  // cnn_opt_fused's rules, plus the step words every mode's ticket uses here
+  if (!cnn_update_valid(u) || u.hp == nullptr || u.step == nullptr || (reinterpret_cast<uintptr_t>(frag) & 15))
+    return hipErrorInvalidValue;
+  // a power-of-two world (the Adasum tree), one flag row and one staging float per parameter for each workgroup,
+  // Gram row b + s inside the workspace
+  if (xv.size < 2 || xv.size > kXgmiMaxRanks || (xv.size & (xv.size - 1)) != 0 || xv.rank < 0 || xv.rank >= xv.size)
+    return hipErrorInvalidValue;
+  if (xv.blocks < ADA_BLOCKS || xv.slot_bytes < static_cast<int64_t>(NPARAM) * 4 || gram == nullptr ||
+      gram_rows < ADA_BLOCKS + ADA_NSEG)
+    return hipErrorInvalidValue;
+  using DeltaFn = decltype(&k_cnn_adasum_delta<0, 2>);
+  using ApplyFn = decltype(&k_cnn_adasum_apply<2>);
+  static const DeltaFn kDelta[3][4] = {
+      {&k_cnn_adasum_delta<0, 2>, &k_cnn_adasum_delta<1, 2>, &k_cnn_adasum_delta<2, 2>, &k_cnn_adasum_delta<3, 2>},
+      {&k_cnn_adasum_delta<0, 4>, &k_cnn_adasum_delta<1, 4>, &k_cnn_adasum_delta<2, 4>, &k_cnn_adasum_delta<3, 4>},
+      {&k_cnn_adasum_delta<0, 8>, &k_cnn_adasum_delta<1, 8>, &k_cnn_adasum_delta<2, 8>, &k_cnn_adasum_delta<3, 8>}};
+  static const ApplyFn kApply[3] = {&k_cnn_adasum_apply<2>, &k_cnn_adasum_apply<4>, &k_cnn_adasum_apply<8>};
+  const int wi = xv.size == 2 ? 0 : xv.size == 4 ? 1 : 2;
+  hipLaunchKernelGGL(kDelta[wi][u.mode], dim3(ADA_BLOCKS), dim3(ADA_T), 0, s, params, grads, u.m, u.v, u.hp, u.step,
+                     xv, kCnnSegEnds, gram);
+  hipLaunchKernelGGL(kApply[wi], dim3(ADA_BLOCKS), dim3(ADA_T), 0, s, params, static_cast<uint16_t*>(frag), xv,
+                     kCnnSegEnds, gram);
   return hipGetLastError();
 }
 

@@ -54,7 +54,8 @@ def build_parser():
     ap.add_argument("--compression", default="none", choices=["none", "fp16", "bf16"])
     ap.add_argument("--use-adasum", action="store_true",
                     help="hvd.Adasum of the per-step weight deltas instead of averaged gradients (the upstream "
-                         "example's switch): layer-by-layer path, power-of-two worlds, no compression")
+                         "example's switch): power-of-two worlds, no compression; on the fused GPU step the two "
+                         "Adasum launches of the fused CNN (PDE_CNN_ADASUM_FUSED=0: the optimizer's own step)")
     add_runtime_args(ap)
     return ap
 
@@ -71,9 +72,9 @@ def main(argv=None):
     loader = ShardedLoader(train_set, args.batch_size, hvd.size(), hvd.rank(), shuffle=True)
 
     model = Net().to(dev)
-    fast = dev.type == "cuda" and not args.layers and not args.use_adasum
+    fast = dev.type == "cuda" and not args.layers
     optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
-    if args.use_adasum:  # (the fused step reduces gradients inside its kernel: Adasum takes the layer path)
+    if args.use_adasum:  # (FusedHvdStep: the fused kernel's local gradients + the two Adasum launches on the deltas)
         optimizer = hvd.DistributedOptimizer(optimizer, named_parameters=model.named_parameters(),
                                              compression=getattr(hvd.Compression, args.compression), op=hvd.Adasum)
     else:
@@ -132,5 +133,7 @@ def main(argv=None):
     dt = time.time() - t0
     print(f"Worker: {hvd.rank()} | {seen / dt:.0f} images/s (this worker) | engine {hvd.engine_stats()}",
           flush=True)
+    # the route the training steps took, for callers and tests: FusedHvdStep.route, or "layers"
+    model.train_route = step.route if step is not None else "layers"
     hvd.shutdown()
     return model

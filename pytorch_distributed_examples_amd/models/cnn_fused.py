@@ -31,6 +31,8 @@ reference's ``optim.SGD(lr=0.01)``, mnist_horovod.py:50 -- or with momentum and 
     loss = fused.forward_backward(x, y, grad_out=ddp.flat_grad)         # world > 1, any data plane:
     ddp.sync_gradients(); fused.opt_step(opt, ddp.flat_grad)            #   3 launches + all-reduce
     loss = fused.forward_backward(x, y, opt=adamw)                      # a FusedAdamW: AdamW in the reduction
+    loss = fused.forward_backward(x, y, grad_out=g)                     # world 2 / 4 / 8 on one node, hvd.Adasum of
+    fused.adasum_step(opt, g, xa)                                       #   the weight deltas: 4 launches
 
 With ``xgmi`` (a :class:`..parallel.xgmi_allreduce.XgmiAllreduce` over the data-parallel ranks) the slab
 reduction exchanges every workgroup's gradient chunk with all peers over xGMI inside the same kernel and
@@ -149,6 +151,21 @@ class FusedCNN:
         the optimiser's own (optim_device.h)."""
         mode, st, params, m, v = self._update_args(opt)
         _native.C().cnn_opt(self.flat, grads, self.frag, st["hp"], st["step"], mode=mode, m=m, v=v)
+        self._after_update(opt, params)
+
+    @torch.no_grad()
+    def adasum_step(self, opt, grads: torch.Tensor, xgmi):
+        """``hvd.Adasum`` of the ranks' weight deltas (``hvd/optimizer.py`` ``_adasum_step``) behind
+        ``forward_backward(x, y, grad_out=grads)``, TWO launches on the current stream: ``k_cnn_adasum_delta`` takes
+        ``opt``'s LOCAL step on ``grads`` (its state and device step counter advance; the weights keep the shared
+        starting values), exchanges the deltas over ``xgmi`` (a one-shot :class:`..parallel.xgmi_allreduce.
+        XgmiAllreduce` over a power-of-two world) and writes every tensor's Gram; ``k_cnn_adasum_apply`` sets
+        ``w = start + adasum_r(delta_r)``, one set of coefficients per parameter tensor, bit-identical on every rank,
+        and refreshes the fragment image.  ``xgmi`` must be idle on every other stream (the hvd engine: graph mode)."""
+        mode, st, params, m, v = self._update_args(opt)
+        gram, rows = xgmi.gram_workspace()
+        _native.C().cnn_adasum_step(self.flat, grads, self.frag, st["hp"], st["step"], mode, m, v,
+                                    xgmi_view=xgmi.view(), gram=gram, gram_rows=rows)
         self._after_update(opt, params)
 
     def sgd_step(self, opt, grads: torch.Tensor):

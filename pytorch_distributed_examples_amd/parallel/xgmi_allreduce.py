@@ -92,6 +92,11 @@ class XgmiAllreduce:
         epilogue: the fused CNN's gradient reduction (``FusedCNN.forward_backward(..., xgmi=self)``)."""
         return self.impl.view()
 
+    def gram_workspace(self) -> tuple:
+        """``(device pointer, rows)`` of the Adasum Gram workspace, for kernels that fold the Adasum exchange into
+        their own launches (``FusedCNN.adasum_step``); allocated at construction, ``(0, 0)`` at world 1."""
+        return tuple(self.impl.gram_workspace())
+
     def check(self, clear: bool = True) -> None:
         """Raise if any call timed out waiting for a peer (or gave up on ``abort()``); synchronises the
         device.  ``clear``: reset the error words first, so the instance is usable again once the caller has
