@@ -237,13 +237,16 @@ __device__ __forceinline__ float wave_max_dpp(float v) { return wave_all(v, [](f
 
 struct CnnSmem {
   // bf16 MFMA operands
-  alignas(16) uint16_t r1n[NI][NC1][C1P];  // relu(maxpool(conv1)) channel-last, ci padded with zeros; e1 (P7b-P9)
-                                           // later, spanning r1n and the front of w2f (both dead after P2)
+  alignas(16) uint16_t r1n[NI][NC1][C1P];  // relu(maxpool(conv1)) channel-last, ci padded with zeros (P1; read by
+                                           // P2 and by P4's transpose into r1); e1 (P7b-P9) later, spanning r1n
+                                           // and the front of w2f (r1n dead after P4, w2f after P2)
   alignas(16) u16x8 w2f[KS2][2][64];   // conv2 fwd B fragments [kstep][ntile][lane]
   alignas(16) u16x8 w2d[KSD][64];      // conv2 dgrad B fragments [kstep][lane]: B[k=(tap,co)][n=ci]
   alignas(16) u16x8 w1f[64];           // conv1 B fragment
   // conv2-output gradient (non-zero only at the argmax taps), twice: channel-last for the dgrad A
-  // fragments (co padded to 32 with zeros) and as 8x8 planes for the wgrad A fragments
+  // fragments (co padded to 32 with zeros) and as 8x8 planes for the wgrad A fragments.  Both are zeroed whole
+  // in P0 (adjacent: one run of 16-byte stores) and have no other tenant until P9's partials alias d2n; P6
+  // stores the live argmax taps only
   alignas(16) uint16_t d2n[NI * D2N_IM];     // (d2n_ofs layout)
   alignas(16) uint16_t d2[NI][C2][D2R];    // rows padded to 144 B: the 16 co rows of a wgrad A fragment hit
                                            // 16 distinct 16-B bank groups (128-B rows: 4-8-way conflicts)
@@ -257,7 +260,9 @@ struct CnnSmem {
   uint16_t xonepad[48];                // xone starts 4 banks after x (36 words): P9's bias-column reads no longer
                                        // share a bank with the tap-(4,4) column (scripts/p9_lds_model.py)
   alignas(16) uint16_t xone[NI][NXP];  // bf16 1.0 everywhere: P9's B column 25 reads it (conv1's bias gradient)
-  alignas(16) uint16_t r1[NI][C1 * RP16];   // relu(maxpool(conv1)), [ci][cell] (pitch RP16)
+  alignas(16) uint16_t r1[NI][C1 * RP16];   // relu(maxpool(conv1)), [ci][cell] (pitch RP16): P7a's B operand,
+                                            // transposed from r1n inside P4 (the cells past NC1 are never written:
+                                            // P7a's reads that touch them shift them out)
   // fp32 head
   alignas(16) float b1[C1];
   alignas(16) float b2[C2];
@@ -452,9 +457,20 @@ __device__ __forceinline__ void cnn_p0(Smem& S, int t, int n0, int B, const floa
     (&S.x1[0][0])[r * XP + H0 - 1 + c] = 0;
   }
   if constexpr (TRAIN) {
-    for (int i = t; i < NI * O2 * O2; i += T) {  // co group 2 zeroed (co 20..23 stay zero; 16..19 rewritten per step)
-      const int im = i / (O2 * O2), pos = i - im * (O2 * O2);
-      *reinterpret_cast<u16x8*>(&S.d2n[d2n_ofs(im, pos / O2, pos % O2, 16)]) = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    // the conv2-output gradient, both layouts, zeroed whole: P6 then stores only the argmax taps.  d2n's extent
+    // [0, NI D2N_IM) holds every slot a P7b A read can touch (co 20..23 and the row / position padding included),
+    // d2 every row a P7a A read does; neither has another tenant before P9's partials
+    constexpr int NZ = (sizeof(Smem::d2n) + sizeof(Smem::d2)) / 16;
+    static_assert(offsetof(Smem, d2) == offsetof(Smem, d2n) + sizeof(Smem::d2n) && sizeof(Smem::d2n) % 16 == 0 &&
+                      sizeof(Smem::d2) % 16 == 0 && NZ > T && NZ <= 2 * T,
+                  "d2n, d2 adjacent: two 16-byte stores per thread");
+    static_assert(sizeof(Smem::d2n) == sizeof(uint16_t) * NI * D2N_IM &&
+                      d2n_ofs(NI - 1, O2 - 1, O2 - 1, CG * 8 - 1) == NI * D2N_IM - 1 && d2n_ofs(0, 0, 0, 0) == 0,
+                  "d2n: the zeroed extent is first to last slot of (image, y, x, co < 24)");
+    {
+      u16x8* z = reinterpret_cast<u16x8*>(&S.d2n[0]);
+      z[t] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (t + T < NZ) z[t + T] = u16x8{0, 0, 0, 0, 0, 0, 0, 0};
     }
     if (t < 8) S.zero16[t] = 0;
     static_assert((NI * NXP) % 8 == 0 && NI * NXP / 8 <= T, "xone: one 16-byte store per thread");
@@ -511,7 +527,8 @@ __device__ __forceinline__ void cnn_p0(Smem& S, int t, int n0, int B, const floa
 
 // ---- The forward P1-P4 of k_cnn_train (TRAIN) and k_cnn_eval: ONE set of functions, so the two kernels run
 // the same device code on the same operands in the same order -- their results agree bit for bit by
-// construction.  TRAIN adds what only the backward reads (r1, a1, a2, h1d) and the dropout masks.
+// construction.  TRAIN adds what only the backward reads (a1, a2, h1d) and the dropout masks; the backward's
+// [ci][cell] copy of r1n (r1) is made later, inside P4, by waves that have nothing else to do there.
 
 // max over a pooling window's 4 taps and the tap that holds it (the first tap wins a tie)
 __device__ __forceinline__ float pool4(const f32x4& v, int& am) {
@@ -526,7 +543,7 @@ __device__ __forceinline__ float pool4(const f32x4& v, int& am) {
 // conv1 tile ownership.  A tile is 4 consecutive pooling cells of one cell row (P1 / 4 tiles per row, MT1 per
 // image).  Wave w owns NT1 CONTIGUOUS tiles: image w / P1_WI, the P1_WR whole cell rows from (w % P1_WI) * P1_WR,
 // its tile u being row u / P1_TR of those, cells 4 (u % P1_TR) .. +3.  Only the wave's first tile depends on the
-// wave id; tile u lies a compile-time distance from it in x, r1n, r1 and a1 alike.  (With the tiles dealt round
+// wave id; tile u lies a compile-time distance from it in x, r1n and a1 alike.  (With the tiles dealt round
 // robin, wid + u NW, none of that folded: every tile carried its own scalar tile / 36, t4 / 3 and remainder
 // chains and its own vector address adds, ~650 issued instructions per wave around 9 MFMAs.)
 static_assert(P1 % 4 == 0 && MT1 * 4 == NC1, "conv1 tiles: 4 cells of one row");
@@ -562,7 +579,7 @@ static_assert(p1_map_ok(), "conv1 wave map: the 16 waves cover each of the NI * 
 // K runs over 6-wide kernel rows (kx = 5 has zero weight): every k pair (kx even) is two consecutive
 // pixels, read as ONE aligned 4-byte LDS load -- from x when the window starts on an even column (dx = 0),
 // from the shifted copy x1 otherwise: 4 gathers per fragment instead of 8.
-// Addresses: each lane forms its 4 gather bases and its 3 store bases (r1n, r1, a1) ONCE, at the wave's first
+// Addresses: each lane forms its 4 gather bases and its 2 store bases (r1n, a1) ONCE, at the wave's first
 // tile (p1_tile above); tile u's distance from it is a constant that rides in the LDS instruction's offset
 // field, and pairs of gathers merge into ds_read2_b32.  The lane -> (cell, tap) mapping inside a tile, and
 // with it the bank pattern of one gather instruction (2.75 LDS cycles, XP above), is the same for every tile.
@@ -629,12 +646,10 @@ __device__ __forceinline__ void cnn_p1(Smem& S, int lane, int wid) {
     // the backward's copies, all tiles under ONE exec region: lanes co >= C1 have none (exec, no per-lane
     // address selects)
     if (co < C1) {
-      uint16_t* r1 = &S.r1[w0.im][co * RP16 + cw];
       unsigned char* a1 = &S.a1[w0.im][co * RP8 + cw];
 #pragma unroll
       for (int u = 0; u < NT1; ++u) {
         const P1Tile q = p1_tile(0, u);
-        r1[q.py * P1 + q.px0] = rr[u];
         a1[q.py * P1 + q.px0] = static_cast<unsigned char>(am[u]);
       }
     }
@@ -808,9 +823,10 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
 
   // ---- P0 (cnn_p0): images -> bf16, conv1's bf16 MFMA fragment, fp32 head weights, dropout masks, tables.
   // Only w1f is stored to LDS now; conv2's forward fragments (w2f, fr) are requested in P0 and stored at the
-  // end of P1, its data-gradient fragments (w2d) are requested in P4 and stored at the end of P6 -- their
-  // latency is on no phase's critical path, and the burst of fragment reads every workgroup makes at the
-  // start is 28 KB instead of 47 KB.
+  // end of P1, its data-gradient fragments (w2d) are requested ahead of P4 and stored inside it by the waves
+  // that have no image there -- their latency is on no phase's critical path, and the burst of fragment reads
+  // every workgroup makes at the start is 28 KB instead of 47 KB.  The conv2-output gradient planes (d2, d2n)
+  // are zeroed here, while the loads are out.
   u16x8 fr[2];  // conv2 forward fragments: stored to LDS at the end of P1
   cnn_p0<true>(S, t, n0, B, images, tgt, params, frag, rng, p_drop2, p_drop1, training, fr);
   float* slab = slabs + static_cast<long>(blockIdx.x) * NSLABP + SLAB_OFS;
@@ -839,10 +855,24 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
   lds_sync();
   PDE_STAMP(4);
 
+  // conv2 data-gradient fragments for P7b, by the waves that have no image in P4 (TW threads, slots iw and
+  // iw + TW): requested ahead of w6, so the counted wait in front of their LDS stores leaves w6 in flight, and
+  // stored inside P4 while the head waves work (the w2d region is idle until P7b).  Under a wave-uniform branch
+  // that only those waves take: loads every wave issued would sink into P4's branch, behind w6
+  constexpr int TW = T - NI * 64;
+  static_assert(NF2D > TW && NF2D <= 2 * TW, "w2d: two fragment slots per thread of the waves past the heads");
+  const int iw = t - NI * 64;
+  u16x8 fd[2];
+  if constexpr (!BREG) {
+    if (wid >= NI) {
+      fd[0] = frag[NF2F + iw];
+      fd[1] = frag[NF2F + min(iw + TW, NF2D - 1)];
+    }
+  }
   // fc1 weight columns for P6's dp2 (thread (i, jc): up to 17 rows of column i), requested now so their L2
   // latency hides under P4 / P5
   // (unconditional loads from clamped addresses -- no divergent branch around them, so the compiler tracks
-  // them precisely; rows past the chunk / threads past NIN x DP2_JC load a valid element P6 never uses)
+  // them precisely; rows past the chunk / threads past NIN x DP2_JC load a valid element whose sum P6 drops)
   constexpr int JPER = F1 - DP2_J * (DP2_JC - 1);  // 18: the longest chunk
   float w6[JPER];
   {
@@ -850,12 +880,6 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
     const int jc = tc / NIN, i = tc - jc * NIN;
 #pragma unroll
     for (int u = 0; u < JPER; ++u) w6[u] = gFC1W[min(jc * DP2_J + u, F1 - 1) * NIN + i];
-  }
-  // conv2 data-gradient fragments for P7b: stored to LDS at the end of P6 (the w2d region is idle until then)
-  u16x8 fd[2];
-  if constexpr (!BREG) {
-    fd[0] = frag[NF2F + t];
-    fd[1] = frag[NF2F + min(t + T, NF2D - 1)];
   }
 
   // ---- P4: fc2 logits, then log_softmax (cnn_head) + NLL + dlogits: ONE WAVE PER IMAGE.
@@ -881,6 +905,34 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
 #pragma unroll
     for (int vv = 0; vv < F2; ++vv) sh += S.fc2w[vv * F1 + j] * lanef(dl, 4 * vv);
     if (lane < F1) S.dh[im][lane] = (S.h1[im][lane] > 0.f) ? sh * S.m1[im][lane] : 0.f;
+  } else {
+    // The waves without an image fill LDS regions that have no reader before P7a / P7b, while the LDS pipe is
+    // nearly idle (straight-line code: a loop header would make the compiler drain w6).
+    // r1, the [ci][cell] planes of P7a's B operand, transposed from the channel-last r1n (the same bf16 bits; r1n
+    // is intact until P7b's epilogue).  Thread = (image, cell pair, channel half h): lane pairs read 32 contiguous
+    // bytes, the two 16-byte reads (even cell, odd cell) are 2-way on the b128 lane groups; a store is the aligned
+    // word {even cell, odd cell} of one channel, consecutive words over consecutive cell pairs.  Half 1 holds
+    // channels 8, 9 and r1n's zero padding.
+    static_assert(NC1 % 2 == 0 && RP16 % 2 == 0 && C1 > 8 && C1 <= 10 && C1P == 16 && NI * NC1 <= TW,
+                  "r1 from r1n: cell pairs as aligned words, channels 0..7 | 8, 9");
+    if (iw < NI * NC1) {
+      const uint32_t uw = static_cast<uint32_t>(iw);  // (unsigned: the divisions are a multiply and shifts)
+      const uint32_t im = uw / NC1, cp = (uw - im * NC1) >> 1, h = uw & 1;
+      const uint32_t* src = reinterpret_cast<const uint32_t*>(&S.r1n[0][0][0]) + (uw >> 1) * C1P + h * 4;
+      const u32x4 ev = *reinterpret_cast<const u32x4*>(src), od = *reinterpret_cast<const u32x4*>(src + C1P / 2);
+      uint32_t* dst = reinterpret_cast<uint32_t*>(&S.r1[im][0]) + h * 8 * (RP16 / 2) + cp;
+#pragma unroll
+      for (int d = 0; d < 4; ++d)
+        if (d == 0 || h == 0) {
+          dst[(2 * d) * (RP16 / 2)] = (ev[d] & 0xFFFFu) | (od[d] << 16);
+          dst[(2 * d + 1) * (RP16 / 2)] = (ev[d] >> 16) | (od[d] & 0xFFFF0000u);
+        }
+    }
+    if constexpr (!BREG) {
+      u16x8* dst = &S.w2d[0][0];
+      dst[iw] = fd[0];
+      if (iw + TW < NF2D) dst[iw + TW] = fd[1];
+    }
   }
   lds_sync();
   PDE_STAMP(5);
@@ -893,6 +945,35 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
   // dp2 = grad at the pooled conv2 output.  Columns n0..n0+3 of the K-contiguous bf16 [row][Bkp] image (the
   // reduction's bf16 MFMA operands): one 8-byte store per row (rows 0..49 dH^T, 50..369 R2^T); the workgroup
   // owning the last columns also zeroes the row padding up to Bkp (a multiple of 8).
+  float* dpart = reinterpret_cast<float*>(&S.w2f[0][0][0]);  // [jc][im][i]
+  // dp2's partial sums first: they are the phase's critical path, and w6's waits are counted ones that must not
+  // see the write-through stores below (inline asm the compiler does not count: behind them the last w6 wait,
+  // vmcnt(0), would wait for every store's acknowledgement).  Every thread consumes its w6 (clamped like the
+  // loads; only the LDS stores are predicated), so no path reaches the rest of the kernel with loads pending
+  {  // thread (i, jc): sum over fc1 outputs j in chunk jc (column loads coalesced)
+    const int tc = min(t, NIN * DP2_JC - 1);
+    const int jc = tc / NIN, i = tc - jc * NIN;
+    const int j0 = jc * DP2_J, nj = jc == DP2_JC - 1 ? F1 - j0 : DP2_J;
+    const float* w = w6;  // loaded before P4
+    float s4[NI] = {0.f, 0.f, 0.f, 0.f};
+    // dh read as float4 (5 per image instead of 18 scalars); products past the chunk are selected away
+    // (the padding columns are never written: select, not multiply by zero)
+#pragma unroll
+    for (int im = 0; im < NI; ++im)
+#pragma unroll
+      for (int q = 0; q < (JPER + 3) / 4; ++q) {
+        const f32x4 d = *reinterpret_cast<const f32x4*>(&S.dh[im][j0 + 4 * q]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int u = 4 * q + e;
+          if (u < JPER) s4[im] += u < nj ? w[u] * d[e] : 0.f;
+        }
+      }
+    if (t < NIN * DP2_JC) {
+#pragma unroll
+      for (int im = 0; im < NI; ++im) dpart[(jc * NI + im) * NIN + i] = s4[im];
+    }
+  }
   static_assert(FC2N + F2 <= T, "fc2 weight / bias gradients: one element per thread");
   if (t < FC2N) {  // fc2 weight gradient (all images' dlog / h1d, complete since P4's barrier)
     const int v = t / F1, j = t - v * F1;
@@ -924,55 +1005,58 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
     for (int im = 0; im < NI; ++im) s += S.dh[im][t];
     out_st<SM>(&slab[S_FC1B + t], s);
   }
-  float* dpart = reinterpret_cast<float*>(&S.w2f[0][0][0]);  // [jc][im][i]
-  if (t < NIN * DP2_JC) {  // thread (i, jc): sum over fc1 outputs j in chunk jc (column loads coalesced)
-    const int jc = t / NIN, i = t - jc * NIN;
-    const int j0 = jc * DP2_J, nj = jc == DP2_JC - 1 ? F1 - j0 : DP2_J;
-    const float* w = w6;  // loaded before P4
-    float s4[NI] = {0.f, 0.f, 0.f, 0.f};
-    // dh read as float4 (5 per image instead of 18 scalars); products past the chunk are selected away
-    // (the padding columns are never written: select, not multiply by zero)
-#pragma unroll
-    for (int im = 0; im < NI; ++im)
-#pragma unroll
-      for (int q = 0; q < (JPER + 3) / 4; ++q) {
-        const f32x4 d = *reinterpret_cast<const f32x4*>(&S.dh[im][j0 + 4 * q]);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int u = 4 * q + e;
-          if (u < JPER) s4[im] += u < nj ? w[u] * d[e] : 0.f;
-        }
-      }
-#pragma unroll
-    for (int im = 0; im < NI; ++im) dpart[(jc * NI + im) * NIN + i] = s4[im];
-  }
   lds_sync();
   // dp2 = grad at the pooled conv2 output, scattered to the argmax taps by the thread that combines it (both
-  // layouts; every tap of every window is written) -- no barrier between the two; the conv2 bias gradient,
-  // which needs every dp2 of a channel, runs after the phase's closing barrier
-  for (int it = t; it < NI * NIN; it += T) {
-    const int im = it / NIN, q = it - im * NIN, co = q / NC2, cell = q - co * NC2;
-    float s1 = 0.f;
+  // layouts) -- no barrier between the two; the conv2 bias gradient, which needs every dp2 of a channel, runs
+  // after the phase's closing barrier.  d2 and d2n were zeroed in P0: only the argmax tap of a live cell is
+  // stored, 2 bytes in each layout (a dead cell's gradient is the zero already there).  ONE trip: thread (image
+  // pair slot, q) takes the element q of images im0 and im0 + NI / 2, every LDS read of both items issued before
+  // the first use
+  constexpr int IH = NI / 2;
+  static_assert(NI % 2 == 0 && IH * NIN <= T, "dp2 scatter: two images per thread, one trip");
+  if (t < IH * NIN) {
+    const int im0 = t / NIN, q = t - im0 * NIN, co = q / NC2, cell = q - co * NC2;
+    const int py = cell >> 2, px = cell & 3;
+    float pj[2][DP2_JC], rv[2], mk[2];
+    int am[2];
 #pragma unroll
-    for (int jc = 0; jc < DP2_JC; ++jc) s1 += dpart[(jc * NI + im) * NIN + q];
-    const float v = (S.r2[im][q] > 0.f) ? s1 * S.mc2[im][co] : 0.f;
-    S.dp2[im][q] = v;
-    const int py = cell >> 2, px = cell & 3, a = S.a2[im][q];
-    const uint16_t g = f2bf(v);
-    const int p00 = (2 * py) * O2 + 2 * px;
-    const uint32_t gv = g;
-    *reinterpret_cast<uint32_t*>(&S.d2[im][co][p00]) = a == 0 ? gv : (a == 1 ? gv << 16 : 0u);
-    *reinterpret_cast<uint32_t*>(&S.d2[im][co][p00 + O2]) = a == 2 ? gv : (a == 3 ? gv << 16 : 0u);
-    uint16_t* dn = &S.d2n[d2n_ofs(im, 2 * py, 2 * px, co)];
-    dn[0] = a == 0 ? g : 0;
-    dn[D2N_P] = a == 1 ? g : 0;
-    dn[D2N_RP] = a == 2 ? g : 0;
-    dn[D2N_RP + D2N_P] = a == 3 ? g : 0;
-  }
-  if constexpr (!BREG) {
-    u16x8* dst = &S.w2d[0][0];
-    dst[t] = fd[0];
-    if (t + T < NF2D) dst[t + T] = fd[1];
+    for (int u = 0; u < 2; ++u) {
+      const int im = im0 + u * IH;
+#pragma unroll
+      for (int jc = 0; jc < DP2_JC; ++jc) pj[u][jc] = dpart[(jc * NI + im) * NIN + q];
+      rv[u] = S.r2[im][q];
+      mk[u] = S.mc2[im][co];
+      am[u] = S.a2[im][q];
+    }
+    // (the values are VGPRs HERE: left alone, the compiler sinks an item's reads into its live-cell region below,
+    // one dependent LDS round trip per item inside divergent code)
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+#pragma unroll
+      for (int jc = 0; jc < DP2_JC; ++jc) asm volatile("" : "+v"(pj[u][jc]));
+      asm volatile("" : "+v"(rv[u]), "+v"(mk[u]), "+v"(am[u]));
+    }
+    float v[2];
+    uint32_t o2[2], on[2];  // u16 index of the argmax tap in d2 / d2n
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int im = im0 + u * IH;
+      float s1 = 0.f;
+#pragma unroll
+      for (int jc = 0; jc < DP2_JC; ++jc) s1 += pj[u][jc];
+      v[u] = rv[u] > 0.f ? s1 * mk[u] : 0.f;
+      S.dp2[im][q] = v[u];
+      const int y = 2 * py + (am[u] >> 1), x = 2 * px + (am[u] & 1);
+      o2[u] = static_cast<uint32_t>((im * C2 + co) * D2R + y * O2 + x);
+      on[u] = static_cast<uint32_t>(d2n_ofs(im, y, x, co));
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+      if (rv[u] > 0.f) {
+        const uint16_t g = f2bf(v[u]);
+        (&S.d2[0][0][0])[o2[u]] = g;
+        S.d2n[on[u]] = g;
+      }
   }
   lds_sync();
   PDE_STAMP(8);
