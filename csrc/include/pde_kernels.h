@@ -378,8 +378,6 @@ hipError_t cnn_opt_fused(float* params, const float* grads, void* frag, const Cn
 // hipErrorInvalidValue where any of it fails.
 hipError_t cnn_adasum_step(float* params, const float* grads, void* frag, const CnnUpdate& u, const XgmiView& xv,
                            double* gram, int gram_rows, hipStream_t s);
-// 1 when the single-process fused tail's grid barrier timed out (PDE_CNN_FUSED_TAIL); reset clears it
-int cnn_tail_error(int reset);
 // Forward-only evaluation of Net (eval mode: no dropout) on the training kernel's operands and precision: one
 // launch (two with prep = 1, which rebuilds the fragment image first), every activation in LDS.  Any B >= 1.
 // Each output is optional (nullptr skips it): logp [B,10] fp32 log-probabilities; pred [B] int64 argmax (the

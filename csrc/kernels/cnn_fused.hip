@@ -179,7 +179,6 @@ __host__ __device__ constexpr uint64_t p7b_pack_map(bool pair) {
   return v;
 }
 constexpr uint64_t P7B_MCLS = p7b_pack_map(false), P7B_MPAIR = p7b_pack_map(true);
-constexpr int XMAP_P7B_FULLK = 8;  // xmap bit: every class runs all KSD k-steps (PDE_CNN_P7B_FULLK, diagnostic)
 // parameter offsets in the flat gradient (torch parameter order of Net)
 constexpr int O_W1 = 0, O_B1 = O_W1 + W1N, O_W2 = O_B1 + C1, O_B2 = O_W2 + W2N, O_FC1W = O_B2 + C2,
               O_FC1B = O_FC1W + FC1N, O_FC2W = O_FC1B + F1, O_FC2B = O_FC2W + FC2N, NPARAM = O_FC2B + F2;
@@ -334,77 +333,15 @@ __device__ __forceinline__ u16x8 lds_read16(uint32_t o) {
 #endif
 }
 
-// Single-process fused tail (cnn_train_fused with PDE_CNN_FUSED_TAIL): after P9 every workgroup of k_cnn_train
-// meets at a grid barrier and the first RED_BLOCKS of them run k_cnn_reduce's roles (slab columns, fc1
-// weight-gradient tiles, loss, SGD + fragment refresh) -- one launch per step instead of two, and no kernel
-// boundary between the slabs' producers and their reducers.  Requires every workgroup resident at once (one
-// 157 KB-LDS workgroup per CU: nwg <= CUs, checked on the host) and nothing else on the device: the barrier's
-// bounded spin (2 s) sets `err` instead of hanging if that is ever violated.
-struct CnnTail {
-  const float* gscale;
-  float* grads;
-  float* loss;
-  unsigned long long* rng;
-  float* params;
-  const float* hp;
-  uint16_t* frag;
-  int* step;
-  unsigned* bar;  // [0] arrival counter, [1] generation
-  int* err;
-  int accumulate, B, on, pad;
-};
-__device__ void cnn_fused_tail(const CnnTail& tl, int rb, f32x4* part, uint32_t* s_epoch, int* s_fail,
-                               const float* slabs, int nwg, const uint16_t* acts, const float* loss_part);
-
-// Grid barrier over co-resident workgroups: every wave's global stores complete, one agent-scope release +
-// arrival per workgroup; the last arrival resets the counter and bumps the generation; the others poll it
-// (bounded), then acquire.
-__device__ __forceinline__ void cnn_grid_barrier(unsigned* bar, unsigned n, int* err, unsigned* s_gen) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned g0 = __hip_atomic_load(bar + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    const unsigned old = __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == n - 1) {
-      __hip_atomic_store(bar, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
-      __hip_atomic_fetch_add(bar + 1, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-      while (__hip_atomic_load(bar + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == g0) {
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) {  // 2 s at 100 MHz
-          __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    *s_gen = g0;
-  }
-  __syncthreads();
-}
-
 // Stores of the per-workgroup outputs the reduction launch reads (slabs, activation columns, loss partials):
-// SM 0 plain, 1 non-temporal, 2 write-through (sc1: the bytes leave the XCD's L2 under the remaining phases
-// instead of at the kernel boundary), 3 write-through for the 8- / 16-byte stores only, the dword ones plain
-// (narrow write-through stores cost several times their bytes' time).  Vector stores only.
-template <int SM>
+// write-through (sc1), so the bytes leave the XCD's L2 under the remaining phases instead of at the kernel
+// boundary (plain and non-temporal stores measured slower: profiles/r4k_cnn_store_modes.txt).  Vector stores only.
 __device__ __forceinline__ void out_st(float* p, float v) {
-  if constexpr (SM == 1) __builtin_nontemporal_store(v, p);
-  else if constexpr (SM == 2) asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-  else *p = v;
+  asm volatile("global_store_dword %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
 }
-template <int SM>
-__device__ __forceinline__ void out_st_u16x4(uint16_t* p, u16x4 v) {
-  if constexpr (SM == 1) __builtin_nontemporal_store(v, reinterpret_cast<u16x4*>(p));
-  else st_vec(reinterpret_cast<u16x4*>(p), v, SM >= 2);
-}
-template <int SM>
+__device__ __forceinline__ void out_st_u16x4(uint16_t* p, u16x4 v) { st_vec(reinterpret_cast<u16x4*>(p), v, true); }
 __device__ __forceinline__ void out_st4(float* p, f32x4 v) {
-  if constexpr (SM == 1) __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p));
-  else if constexpr (SM >= 2) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-  else *reinterpret_cast<f32x4*>(p) = v;
+  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
 }
 
 // ---- P0 of k_cnn_train (TRAIN) and k_cnn_eval: images -> bf16 (x, x1), conv1's fragment, the fp32 head
@@ -784,10 +721,6 @@ __device__ __forceinline__ CnnHead cnn_head(const Smem& S, const float* h, int i
   return {logit, lse, ly, y};
 }
 
-// BREG: P7b's B operand (the conv2 data-gradient fragments, identical for every wave) is loaded from the
-// fragment image into registers at the start of P7a instead of being staged in LDS -- a quarter of P7b's LDS
-// traffic moves to the vector-memory path (L1 / L2 hits), which runs beside the LDS.
-template <int SM, bool BREG>
 __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ images, const int64_t* __restrict__ tgt,
                                                  int B, const float* __restrict__ params,
                                                  const u16x8* __restrict__ frag,
@@ -795,17 +728,17 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
                                                  float p_drop1, int training, float* __restrict__ slabs,
                                                  float* __restrict__ loss_part, uint16_t* __restrict__ acts,
                                                  unsigned long long* __restrict__ stamps, int stop_after,
-                                                 CnnTail tail, int xmap) {
+                                                 int fullk) {
   // optional phase timestamps (diagnostic only: stamps == nullptr in production launches); stop_after = k
   // ends the kernel after phase stamp k (diagnostic: hardware counters of a kernel prefix)
 #define PDE_STAMP(k)                                                                      \
   if (stamps != nullptr && threadIdx.x == 0) stamps[blockIdx.x * 16 + (k)] = wall_clock64(); \
   if (stop_after == (k)) return
   // every argument P0 and the stamps read is live here: the kernel-argument segment arrives behind ONE wait
-  // (left to the compiler, stamps / stop_after / xmap / frag each cost P0 a scalar round trip of their own)
+  // (left to the compiler, stamps / stop_after / fullk / frag each cost P0 a scalar round trip of their own)
   asm volatile("" ::"s"(images), "s"(tgt), "s"(B), "s"(params), "s"(frag), "s"(rng), "s"(p_drop2), "s"(p_drop1),
-               "s"(training), "s"(slabs), "s"(loss_part), "s"(acts), "s"(stamps), "s"(stop_after), "s"(xmap),
-               "s"(tail.accumulate), "s"(tail.B), "s"(tail.on), "s"(gridDim.x));
+               "s"(training), "s"(slabs), "s"(loss_part), "s"(acts), "s"(stamps), "s"(stop_after), "s"(fullk),
+               "s"(gridDim.x));
   PDE_STAMP(0);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   CnnSmem& S = *reinterpret_cast<CnnSmem*>(smem_raw);
@@ -816,10 +749,7 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
   const float* gW1 = params + O_W1;
   const float* gW2 = params + O_W2;
   const float* gFC1W = params + O_FC1W;
-  // xmap: workgroups that share an XCD (blockIdx % 8 under the observed round-robin placement) take
-  // consecutive images, so the 8 workgroups writing one 128-B line of an activation row sit behind one L2
-  const int lwg = (xmap & 1) ? (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3) : blockIdx.x;
-  const int n0 = lwg * NI;
+  const int n0 = blockIdx.x * NI;
 
   // ---- P0 (cnn_p0): images -> bf16, conv1's bf16 MFMA fragment, fp32 head weights, dropout masks, tables.
   // Only w1f is stored to LDS now; conv2's forward fragments (w2f, fr) are requested in P0 and stored at the
@@ -840,8 +770,7 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
     if (t == 0) stamps[blockIdx.x * 16 + 13] = wall_clock64();
     if (t == 15 * 64) stamps[blockIdx.x * 16 + 15] = wall_clock64();
   }
-  // (xmap & 2: timing diagnostic, the stores and their wait skipped -- results invalid)
-  if (!(xmap & 2)) cnn_store_w2f(S, t, fr);
+  cnn_store_w2f(S, t, fr);
   lds_sync();
   PDE_STAMP(2);
 
@@ -863,11 +792,9 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
   static_assert(NF2D > TW && NF2D <= 2 * TW, "w2d: two fragment slots per thread of the waves past the heads");
   const int iw = t - NI * 64;
   u16x8 fd[2];
-  if constexpr (!BREG) {
-    if (wid >= NI) {
-      fd[0] = frag[NF2F + iw];
-      fd[1] = frag[NF2F + min(iw + TW, NF2D - 1)];
-    }
+  if (wid >= NI) {
+    fd[0] = frag[NF2F + iw];
+    fd[1] = frag[NF2F + min(iw + TW, NF2D - 1)];
   }
   // fc1 weight columns for P6's dp2 (thread (i, jc): up to 17 rows of column i), requested now so their L2
   // latency hides under P4 / P5
@@ -928,11 +855,9 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
           dst[(2 * d + 1) * (RP16 / 2)] = (ev[d] >> 16) | (od[d] & 0xFFFF0000u);
         }
     }
-    if constexpr (!BREG) {
-      u16x8* dst = &S.w2d[0][0];
-      dst[iw] = fd[0];
-      if (iw + TW < NF2D) dst[iw + TW] = fd[1];
-    }
+    u16x8* dst = &S.w2d[0][0];
+    dst[iw] = fd[0];
+    if (iw + TW < NF2D) dst[iw + TW] = fd[1];
   }
   lds_sync();
   PDE_STAMP(5);
@@ -980,13 +905,13 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
     float s = 0.f;
 #pragma unroll
     for (int im = 0; im < NI; ++im) s += S.dlog[im][v] * S.h1d[im][j];
-    out_st<SM>(&slab[S_FC2W + t], s);
+    out_st(&slab[S_FC2W + t], s);
   } else if (t < FC2N + F2) {
     const int v = t - FC2N;
     float s = 0.f;
 #pragma unroll
     for (int im = 0; im < NI; ++im) s += S.dlog[im][v];
-    out_st<SM>(&slab[S_FC2B + v], s);
+    out_st(&slab[S_FC2B + v], s);
   }
   {
     const int Bk = gridDim.x * NI, Bkp = act_pitch(gridDim.x);
@@ -995,15 +920,15 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
       u16x4 v;
 #pragma unroll
       for (int im = 0; im < NI; ++im) v[im] = f2bf(row < F1 ? S.dh[im][row] : S.r2[im][row - F1]);
-      out_st_u16x4<SM>(acts + static_cast<long>(row) * Bkp + n0, v);
-      if (pad) out_st_u16x4<SM>(acts + static_cast<long>(row) * Bkp + n0 + NI, u16x4{0, 0, 0, 0});
+      out_st_u16x4(acts + static_cast<long>(row) * Bkp + n0, v);
+      if (pad) out_st_u16x4(acts + static_cast<long>(row) * Bkp + n0 + NI, u16x4{0, 0, 0, 0});
     }
   }
   if (t < F1) {
     float s = 0.f;
 #pragma unroll
     for (int im = 0; im < NI; ++im) s += S.dh[im][t];
-    out_st<SM>(&slab[S_FC1B + t], s);
+    out_st(&slab[S_FC1B + t], s);
   }
   lds_sync();
   // dp2 = grad at the pooled conv2 output, scattered to the argmax taps by the thread that combines it (both
@@ -1067,16 +992,7 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
     for (int im = 0; im < NI; ++im)
 #pragma unroll
       for (int c = 0; c < NC2; c += 4) s4 += *reinterpret_cast<const f32x4*>(&S.dp2[im][co * NC2 + c]);
-    out_st<SM>(&slab[O_B2 + co], (s4[0] + s4[1]) + (s4[2] + s4[3]));
-  }
-  // BREG: the first KSB k-steps' B fragments of P7b requested now, ahead of P7a's slab stores (vmcnt retires
-  // in issue order, so waiting for them never waits for those stores); P7b's k-step ks requests k-step
-  // ks + KSB (all 19 held at once: 76 VGPRs, spills)
-  constexpr int KSB = 8;
-  u16x8 bd[BREG ? KSD : 1];
-  if constexpr (BREG) {
-#pragma unroll
-    for (int ks = 0; ks < KSB; ++ks) bd[ks] = frag[NF2F + ks * 64 + lane];
+    out_st(&slab[O_B2 + co], (s4[0] + s4[1]) + (s4[2] + s4[3]));
   }
 
   // ---- P7a: conv2 wgrad (MFMA): dW2[co][(ci,ky,kx)] = sum_(im,y,x) d2[co][y][x] * r1[ci][y+ky][x+kx].
@@ -1131,7 +1047,7 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
 #pragma unroll
       for (int u = 0; u < NT2; ++u) {
         const int kidx = (wid * NT2 + u) * 16 + lr, cg = mt * 4 + lg;
-        if (cg * 4 < C2 && kidx < K2) out_st4<SM>(&slab[O_W2 + (cg * K2 + kidx) * 4], acc[mt][u]);
+        if (cg * 4 < C2 && kidx < K2) out_st4(&slab[O_W2 + (cg * K2 + kidx) * 4], acc[mt][u]);
       }
   }
   PDE_STAMP(9);
@@ -1149,8 +1065,6 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
     const int cls0 = static_cast<int>(P7B_MCLS >> (4 * wid)) & 15;            // wave-uniform, scalar
     const int im0 = (static_cast<int>(P7B_MPAIR >> (4 * wid)) & 1) * MAXT;    // images im0, im0 + 1
     const int npass = cls0 == 0 ? 2 : 1;  // the class-0 waves go on with class MTD - 1
-    // (BREG keeps every k-step: a run-time index into its register-held fragments would go to scratch)
-    const bool fullk = BREG || (xmap & XMAP_P7B_FULLK) != 0;
     // LDS addresses as 32-bit offsets (the A reads select between two of them)
     const uint32_t sbase = lds_addr(smem_raw);
     const uint32_t zpo = sbase + static_cast<uint32_t>(offsetof(CnnSmem, zero16));  // the zero block
@@ -1159,6 +1073,7 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
     uint32_t* e1 = reinterpret_cast<uint32_t*>(&S.r1n[0][0][0]);
     auto run_pass = [&](int pass) {
       const int cls = pass == 0 ? cls0 : MTD - 1;
+      // (fullk: every class runs all KSD k-steps -- PDE_CNN_P7B_FULLK, diagnostic)
       const int lo = fullk ? 0 : static_cast<int>(P7B_LO >> (5 * cls)) & 31;
       const int hi = fullk ? KSD : static_cast<int>(P7B_HI >> (5 * cls)) & 31;
       // (4x4-block tiles model fewer bank conflicts, 6.8 -> 6.0 LDS cycles per A read, but measured slower:
@@ -1198,64 +1113,40 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
           a[u] = lds_read16(o);
         }
       };
-      if constexpr (BREG) {
-        u16x8 an[MAXT];
-        load(tab(0), an);
-        u32x2 en = tab(1);
+      // a scalar-counted loop over [lo, hi), two k-steps per trip on alternating operand registers (ae / be,
+      // ao / bo): reads of k-step ks+1 are issued before the MFMAs of ks, one accumulator per tile in ascending
+      // ks.  (The 19 steps unrolled, each under a wave-uniform lo <= ks < hi guard, index w2d / p7tab by
+      // constants but measured no faster than without ranges: P7b 4.44 against 3.88 us, 34.5 against 28.1 KB
+      // of code, profiles/r7_cnn_train_regs.md)
+      u16x8 ae[MAXT], ao[MAXT], be, bo;
+      load(tab(lo), ae);
+      be = S.w2d[lo][lane];
+      u32x2 en = tab(lo + 1);
+      int ks = lo;
+      for (; ks + 2 < hi; ks += 2) {  // straight-line trips: k-steps ks (ae, be), ks + 1 (ao, bo)
+        u32x2 e = en;
+        en = tab(ks + 2);
+        load(e, ao);
+        bo = S.w2d[ks + 1][lane];
 #pragma unroll
-        for (int ks = 0; ks < KSD; ++ks) {  // reads of k-step ks+1 are issued before the MFMAs of ks
-          u16x8 ac[MAXT];
+        for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ae[u], be, acc[u]);
+        e = en;
+        en = tab(ks + 3);
+        load(e, ae);
+        be = S.w2d[ks + 2][lane];
 #pragma unroll
-          for (int u = 0; u < MAXT; ++u) ac[u] = an[u];
-          if (ks + KSB < KSD) bd[ks + KSB] = frag[NF2F + (ks + KSB) * 64 + lane];
-          if (ks + 1 < KSD) {
-            const u32x2 e = en;
-            en = tab(ks + 2);
-            load(e, an);
-          }
+        for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ao[u], bo, acc[u]);
+      }
+      if (ks + 1 < hi) {  // two k-steps left, or one
+        load(en, ao);
+        bo = S.w2d[ks + 1][lane];
 #pragma unroll
-          for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ac[u], bd[ks], acc[u]);
-        }
-        if (pass + 1 < npass) {  // the second class starts over from k-step 0
+        for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ae[u], be, acc[u]);
 #pragma unroll
-          for (int ks = 0; ks < KSB; ++ks) bd[ks] = frag[NF2F + ks * 64 + lane];
-        }
+        for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ao[u], bo, acc[u]);
       } else {
-        // a scalar-counted loop over [lo, hi), two k-steps per trip on alternating operand registers (ae / be,
-        // ao / bo): reads of k-step ks+1 are issued before the MFMAs of ks, one accumulator per tile in ascending
-        // ks.  (The 19 steps unrolled, each under a wave-uniform lo <= ks < hi guard, index w2d / p7tab by
-        // constants but measured no faster than without ranges: P7b 4.44 against 3.88 us, 34.5 against 28.1 KB
-        // of code, profiles/r7_cnn_train_regs.md)
-        u16x8 ae[MAXT], ao[MAXT], be, bo;
-        load(tab(lo), ae);
-        be = S.w2d[lo][lane];
-        u32x2 en = tab(lo + 1);
-        int ks = lo;
-        for (; ks + 2 < hi; ks += 2) {  // straight-line trips: k-steps ks (ae, be), ks + 1 (ao, bo)
-          u32x2 e = en;
-          en = tab(ks + 2);
-          load(e, ao);
-          bo = S.w2d[ks + 1][lane];
 #pragma unroll
-          for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ae[u], be, acc[u]);
-          e = en;
-          en = tab(ks + 3);
-          load(e, ae);
-          be = S.w2d[ks + 2][lane];
-#pragma unroll
-          for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ao[u], bo, acc[u]);
-        }
-        if (ks + 1 < hi) {  // two k-steps left, or one
-          load(en, ao);
-          bo = S.w2d[ks + 1][lane];
-#pragma unroll
-          for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ae[u], be, acc[u]);
-#pragma unroll
-          for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ao[u], bo, acc[u]);
-        } else {
-#pragma unroll
-          for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ae[u], be, acc[u]);
-        }
+        for (int u = 0; u < MAXT; ++u) acc[u] = mfma(ae[u], be, acc[u]);
       }
       // epilogue: the lane's 4 consecutive cells as e1 words (relu'(r1) from a1's dead mark), one 16-byte store
       if (ci < C1) {
@@ -1272,12 +1163,7 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
         }
       }
     };
-    if constexpr (BREG) {  // straight-line passes: the fragment registers keep compile-time indices and live ranges
-      run_pass(0);
-      if (npass > 1) run_pass(1);
-    } else {
-      for (int pass = 0; pass < npass; ++pass) run_pass(pass);
-    }
+    for (int pass = 0; pass < npass; ++pass) run_pass(pass);
   }
   lds_sync();
   PDE_STAMP(10);
@@ -1372,8 +1258,7 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
       const f32x4 q{s, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, si, 0x55, 0xF, 0xF, false)),
                     __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, si, 0xAA, 0xF, 0xF, false)),
                     __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, si, 0xFF, 0xF, 0xF, false))};
-      if (live && (t & 3) == 0 && !(xmap & 4))  // (xmap & 4: timing diagnostic, stores skipped)
-        out_st4<SM>(&slab[O_W1 + t], q);
+      if (live && (t & 3) == 0) out_st4(&slab[O_W1 + t], q);
     }
   }
   PDE_STAMP(11);
@@ -1381,21 +1266,12 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
   // loss partial: the images' terms from P4
   if (wid == 0) {
     const float l = wave_sum_dpp(lane < NI ? S.lossim[lane] : 0.f);
-    if (lane == 0) out_st<SM>(&loss_part[blockIdx.x], l);
+    if (lane == 0) out_st(&loss_part[blockIdx.x], l);
   }
   if (stamps != nullptr) {  // diagnostic: every wave's stores drained, then the workgroup's last stamp
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     PDE_STAMP(12);
-  }
-  if (tail.on) {  // single process: the reduction roles in this launch (see CnnTail)
-    __shared__ uint32_t s_epoch;
-    __shared__ int s_fail;
-    __shared__ unsigned s_gen;
-    cnn_grid_barrier(tail.bar, gridDim.x, tail.err, &s_gen);
-    // (w2f / w2d are dead after P9: the roles' 8 KB of partials live there)
-    cnn_fused_tail(tail, blockIdx.x, reinterpret_cast<f32x4*>(&S.w2f[0][0][0]), &s_epoch, &s_fail, slabs,
-                   gridDim.x, acts, loss_part);
   }
 }
 
@@ -1466,7 +1342,7 @@ __global__ __launch_bounds__(256) void k_cnn_sgd(float* __restrict__ params, con
   write_frag(frag, p, w);
 }
 
-// grads (+)= gscale / B * (sum_wg slabs[wg] | dH^T . R2) in a fixed order (deterministic).
+// grads (+)= 1 / B * (sum_wg slabs[wg] | dH^T . R2) in a fixed order (deterministic).
 //  * slab blocks (blockIdx < RED_SLAB_BLOCKS): 8 waves over 16 float4 slab columns; lane = column + 16 x
 //    slab-lane, so one load instruction of a wave reads 4 slabs x 256 B and each thread keeps nwg/32
 //    independent float4 loads in flight;
@@ -1478,10 +1354,8 @@ __global__ __launch_bounds__(256) void k_cnn_sgd(float* __restrict__ params, con
 //  * block 0 also reduces the per-workgroup loss partials and advances the dropout RNG counter.
 // With hp (single process, no all-reduce in between) every block also applies the SGD update to the
 // parameters it reduced and refreshes their bf16 fragment slots.
-#ifndef PDE_CNN_RED_COLS
-#define PDE_CNN_RED_COLS 16  // slab columns per reduce block (8: 183 blocks, measured slower, r4ag)
-#endif
-constexpr int RED_T = 512, RED_COLS = PDE_CNN_RED_COLS, RED_LANES = RED_T / RED_COLS;  // slab lanes per column
+constexpr int RED_COLS = 16;  // slab columns per reduce block (8: 183 blocks, measured slower, r4ag)
+constexpr int RED_T = 512, RED_LANES = RED_T / RED_COLS;  // slab lanes per column
 constexpr int NSLAB4 = NSLAB / 4;
 constexpr int RED_SLAB_BLOCKS = (NSLAB4 + RED_COLS - 1) / RED_COLS;
 constexpr int FC1_JT = (F1 + 15) / 16, FC1_IT = NIN / 16;   // 4 x 20 output tiles
@@ -1498,9 +1372,8 @@ __device__ __forceinline__ void sgd_update(float* params, float lr, float gsc, u
 }
 
 // One reduction role (rb = role block: slab columns for rb < RED_SLAB_BLOCKS, else an fc1 weight-gradient
-// tile; role 0 also reduces the loss partials and advances the dropout RNG / SGD step counters), run by the
-// first RED_T threads of a block whose every thread calls it (block barriers inside).  Called by k_cnn_reduce
-// (one role per block) and, single process, by k_cnn_train's workgroups after a grid barrier.
+// tile; role 0 also reduces the loss partials and advances the dropout RNG / SGD step counters), run by every
+// thread of a RED_T block (block barriers inside): k_cnn_reduce, one role per block.
 //
 // OPT: the update the role applies when hp != nullptr.  0: plain SGD (sgd_update above; role 0 counts the step);
 // 1: SGD with momentum and / or L2 weight decay; 2: Adam (L2); 3: AdamW -- optdev::update<OPT - 1> on the final
@@ -1512,15 +1385,17 @@ __device__ __forceinline__ void sgd_update(float* params, float lr, float gsc, u
 template <int OPT>
 __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s_epoch, int* s_fail,
                                                 const float* __restrict__ slabs, int nwg,
-                                                const uint16_t* __restrict__ acts, const float* __restrict__ gscale,
-                                                float* __restrict__ grads, int accumulate,
-                                                const float* __restrict__ loss_part, int B, float* __restrict__ loss,
+                                                const uint16_t* __restrict__ acts, float* __restrict__ grads,
+                                                int accumulate, const float* __restrict__ loss_part, int B,
+                                                float* __restrict__ loss,
                                                 unsigned long long* __restrict__ rng, float* __restrict__ params,
                                                 const float* __restrict__ hp, uint16_t* __restrict__ frag,
                                                 int* __restrict__ step, const XgmiView& xv, float xscale,
                                                 float* __restrict__ om = nullptr, float* __restrict__ ov = nullptr) {
   const int tid = threadIdx.x;
-  const bool act = tid < RED_T;  // (k_cnn_train's threads past RED_T only join the barriers)
+  // always true in a RED_T block; the predicate stays because without it the compiler gives k_cnn_reduce<0> 84
+  // VGPRs instead of 82 (profiles/r12_cnn_one_build.md)
+  const bool act = tid < RED_T;
   int* s_stepw = nullptr;  // OPT != 0: the step being taken (1-based), one word per block
   int step0 = 0;
   if constexpr (OPT != 0) {
@@ -1555,17 +1430,15 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
   // slot, flags, read all ranks' values in rank order, x xscale) before the store + SGD update
   const bool xchg = xv.size > 1;
   // Each role requests its first batch of reduction operands (8 slab loads / 2 x CH activation loads) BEFORE
-  // the small operands: gscale[0], the hyper-parameters and the owner's params / grads do not depend on the
-  // reduction and are requested right behind that batch, as vector loads -- as scalar loads they were a wait
-  // for a memory round trip in front of the first slab request.
-  // k_cnn_train leaves its gradients unscaled (sums over the images, not means): 1 / B is applied here, in fp32,
-  // together with gscale
+  // the small operands: the hyper-parameters and the owner's params / grads do not depend on the reduction and
+  // are requested right behind that batch, as vector loads -- as scalar loads they were a wait for a memory
+  // round trip in front of the first slab request.
+  // k_cnn_train leaves its gradients unscaled (sums over the images, not means): 1 / B is applied here, in fp32
   const float inv_b = 1.f / static_cast<float>(B);
-  float gs = 1.f, lrate = 0.f, gsc = 0.f;
+  float lrate = 0.f, gsc = 0.f;
   auto load_scalars = [&]() {
     int z = 0;  // a per-lane offset the compiler cannot prove uniform: global (vector) loads
     asm("" : "+v"(z));
-    if (gscale) gs = gscale[z];
     if (hp) {
       lrate = hp[HP_LR + z];
       gsc = hp[HP_GRAD_SCALE + z];
@@ -1652,7 +1525,7 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
       v = part[col];
 #pragma unroll 8
       for (int k = 1; k < RED_LANES; ++k) v += part[k * RED_COLS + col];
-      v *= gs * inv_b;
+      v *= inv_b;
       if (xchg) reinterpret_cast<f32x4*>(xmine)[p4] = v;
     }
     bool ok = true;
@@ -1771,7 +1644,7 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
       v = wpart[lane];
 #pragma unroll
       for (int w = 1; w < RED_T / 64; ++w) v += wpart[w * 64 + lane];
-      v *= gs * inv_b;
+      v *= inv_b;
       if (xchg) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1823,7 +1696,7 @@ __device__ __forceinline__ void cnn_reduce_role(int rb, f32x4* part, uint32_t* s
       }
     }
   }
-  if (rb == 0 && tid >= RED_T - 64 && tid < RED_T) {  // role 0's last active wave: loss
+  if (rb == 0 && tid >= RED_T - 64 && tid < RED_T) {  // role 0's last wave: loss
     const int lane = tid - (RED_T - 64);
     float s = 0.f;
     for (int b = lane; b < nwg; b += 64) s += loss_part[b];
@@ -1860,32 +1733,22 @@ __device__ __forceinline__ void arg_live(A a) {
 // (float* om, float* ov) of cnn_reduce_role's stateful modes.
 template <int OPT, class... State>
 __global__ __launch_bounds__(RED_T) void k_cnn_reduce(const float* __restrict__ slabs, int nwg,
-                                                      const uint16_t* __restrict__ acts,
-                                                      const float* __restrict__ gscale, float* __restrict__ grads,
+                                                      const uint16_t* __restrict__ acts, float* __restrict__ grads,
                                                       int accumulate, const float* __restrict__ loss_part, int B,
                                                       float* __restrict__ loss, unsigned long long* __restrict__ rng,
                                                       float* __restrict__ params, const float* __restrict__ hp,
                                                       uint16_t* __restrict__ frag, int* __restrict__ step,
-                                                      XgmiView xv, float xscale, int rb0, State... state) {
+                                                      XgmiView xv, float xscale, State... state) {
   static_assert(sizeof...(State) == (OPT != 0 ? 2 : 0), "the stateful modes take om and ov");
   __shared__ f32x4 part[RED_LANES * RED_COLS];  // slab: [lane][column]; fc1: [wave][lane] (same 8 KB)
   __shared__ uint32_t s_epoch;
   __shared__ int s_fail;
   // every argument live here: the kernel-argument segment arrives behind one wait, ahead of the first request
-  asm volatile("" ::"s"(slabs), "s"(nwg), "s"(acts), "s"(gscale), "s"(grads), "s"(accumulate), "s"(loss_part), "s"(B),
-               "s"(loss), "s"(rng), "s"(params), "s"(hp), "s"(frag), "s"(step), "s"(xv.size), "s"(xscale), "s"(rb0));
+  asm volatile("" ::"s"(slabs), "s"(nwg), "s"(acts), "s"(grads), "s"(accumulate), "s"(loss_part), "s"(B), "s"(loss),
+               "s"(rng), "s"(params), "s"(hp), "s"(frag), "s"(step), "s"(xv.size), "s"(xscale));
   (arg_live(state), ...);
-  cnn_reduce_role<OPT>(rb0 + blockIdx.x, part, &s_epoch, &s_fail, slabs, nwg, acts, gscale, grads, accumulate,
-                       loss_part, B, loss, rng, params, hp, frag, step, xv, xscale, state...);
-}
-
-__device__ void cnn_fused_tail(const CnnTail& tl, int rb, f32x4* part, uint32_t* s_epoch, int* s_fail,
-                               const float* slabs, int nwg, const uint16_t* acts, const float* loss_part) {
-  if (rb >= RED_BLOCKS) return;  // block-uniform: workgroups past the roles are done
-  XgmiView one{};
-  one.size = 1;
-  cnn_reduce_role<0>(rb, part, s_epoch, s_fail, slabs, nwg, acts, tl.gscale, tl.grads, tl.accumulate, loss_part,
-                     tl.B, tl.loss, tl.rng, tl.params, tl.hp, tl.frag, tl.step, one, 1.f);
+  cnn_reduce_role<OPT>(blockIdx.x, part, &s_epoch, &s_fail, slabs, nwg, acts, grads, accumulate, loss_part, B, loss,
+                       rng, params, hp, frag, step, xv, xscale, state...);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2024,60 +1887,12 @@ __global__ __launch_bounds__(T) void k_cnn_eval(const float* __restrict__ images
 }  // namespace
 
 int cnn_num_params() { return NPARAM; }
-// PDE_CNN_FUSED_TAIL=1: the single-process reduction inside k_cnn_train (CnnTail).  Off: measured SLOWER
-// (r3v: 0.054 vs 0.041 ms/step) -- the grid barrier's agent-scope release / acquire in every workgroup writes
-// back and invalidates the L2 of all 8 XCDs 256 times, where the kernel boundary does it once.
-bool cnn_fused_tail_enabled() {
-  const char* e = std::getenv("PDE_CNN_FUSED_TAIL");
-  return e != nullptr && e[0] == '1';
-}
 // PDE_CNN_P7B_FULLK=1 (diagnostic, read on every call): conv2's data gradient runs all KSD k-steps for every
 // tile class instead of the class's own range (p7b_ks_range) -- the skipped steps add exact zeros, so the two
 // must agree bit for bit.
 static bool cnn_p7b_fullk_enabled() {
   const char* e = std::getenv("PDE_CNN_P7B_FULLK");
   return e != nullptr && e[0] == '1';
-}
-int cnn_device_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop{};
-    cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-              ? prop.multiProcessorCount : -1;
-  }
-  return cus;
-}
-// The barrier's counter / generation words and error flag: one zeroed allocation per device, made outside any
-// graph capture (until then the two-launch form runs).
-bool cnn_barrier_words(hipStream_t s, unsigned** bar, int** err) {
-  static unsigned* base[64] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
-  if (base[dev] == nullptr) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return false;
-    void* p = nullptr;
-    if (hipMalloc(&p, 64) != hipSuccess) return false;
-    if (hipMemset(p, 0, 64) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-      (void)hipFree(p);
-      return false;
-    }
-    base[dev] = static_cast<unsigned*>(p);
-  }
-  *bar = base[dev];
-  *err = reinterpret_cast<int*>(base[dev] + 4);
-  return true;
-}
-int cnn_tail_error(int reset) {
-  unsigned* bar = nullptr;
-  int* err = nullptr;
-  if (!cnn_barrier_words(nullptr, &bar, &err)) return 0;
-  int v = 0;
-  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, err, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess)
-    return -1;
-  if (reset && v != 0) (void)hipMemset(err, 0, sizeof(int));
-  return v;
 }
 
 size_t cnn_frag_bytes() { return sizeof(u16x8) * NFRAG; }
@@ -2097,10 +1912,6 @@ bool cnn_update_valid(const CnnUpdate& u) {
 hipError_t cnn_train_fused(const CnnTrainArgs& a, hipStream_t s) {
   const CnnUpdate& u = a.update;
   const int nwg = a.nwg;
-  // The kernels still take a device pointer to a gradient scale (k_cnn_reduce's gscale, CnnTail::gscale) that no
-  // caller ever set: the launcher passes nullptr.  Taking the parameter out changes the kernels, so it is a change
-  // of its own, with a benchmark.
-  const float* const gscale = nullptr;
   if (reinterpret_cast<uintptr_t>(a.grads) & 15) return hipErrorInvalidValue;  // float4 gradient stores
   if (!cnn_update_valid(u)) return hipErrorInvalidValue;
   XgmiView view{};
@@ -2113,67 +1924,31 @@ hipError_t cnn_train_fused(const CnnTrainArgs& a, hipStream_t s) {
     view = *a.xv;
   }
   const size_t sm = sizeof(CnnSmem);
-  // PDE_CNN_STORE: store flavour of the slabs / activations (out_st).  Write-through (2) is the default: the
-  // 7.5 MB the reduction launch reads no longer sit dirty in the XCD L2s at the kernel boundary (r4k: 0.0408 ->
-  // 0.0381 ms/step; non-temporal 0.0390).  PDE_CNN_XMAP=1: XCD-grouped images (r4k: level, off)
-  static const int smode = std::getenv("PDE_CNN_STORE") ? std::atoi(std::getenv("PDE_CNN_STORE")) : 2;
-  static const int xmap_env = std::getenv("PDE_CNN_XMAP") ? std::atoi(std::getenv("PDE_CNN_XMAP")) : 0;
-  static const int diag_frag = (std::getenv("PDE_CNN_DIAG_FRAG") ? 2 : 0) |  // timing only: see k_cnn_train
-                               (std::getenv("PDE_CNN_DIAG_P9ST") ? 4 : 0);
-  const int xmap = (xmap_env != 0 && nwg % 8 == 0 ? 1 : 0) | diag_frag |
-                   (cnn_p7b_fullk_enabled() ? XMAP_P7B_FULLK : 0);
-  static const bool breg = std::getenv("PDE_CNN_BREG") != nullptr && std::getenv("PDE_CNN_BREG")[0] == '1';
-  using TrainFn = decltype(&k_cnn_train<0, false>);
-  static const TrainFn kTrain[2][4] = {
-      {&k_cnn_train<0, false>, &k_cnn_train<1, false>, &k_cnn_train<2, false>, &k_cnn_train<3, false>},
-      {&k_cnn_train<0, true>, &k_cnn_train<1, true>, &k_cnn_train<2, true>, &k_cnn_train<3, true>}};
-  const int si = smode >= 0 && smode <= 3 ? smode : 0;
-  const TrainFn train = kTrain[breg ? 1 : 0][si];
-  static bool attr[2][4] = {};
-  if (!attr[breg ? 1 : 0][si]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(train), hipFuncAttributeMaxDynamicSharedMemorySize,
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cnn_train), hipFuncAttributeMaxDynamicSharedMemorySize,
                               static_cast<int>(sm));
-    attr[breg ? 1 : 0][si] = true;
+    attr = true;
   }
   if (reinterpret_cast<uintptr_t>(a.frag) & 15) return hipErrorInvalidValue;
   if (a.prep)
     hipLaunchKernelGGL(k_cnn_prep, dim3(ceil_div(NFRAG, 256)), dim3(256), 0, s, a.params,
                        static_cast<u16x8*>(a.frag));
   if (reinterpret_cast<uintptr_t>(a.acts) & 15) return hipErrorInvalidValue;
-  CnnTail tail{};
-  unsigned* bar = nullptr;
-  int* berr = nullptr;
-  // (the stateful updates always take the two-launch form: the tail is instantiated for plain SGD only)
-  if (u.mode == CNN_SGD && view.size == 1 && a.stamps == nullptr && a.stop_after < 0 && cnn_fused_tail_enabled() &&
-      nwg >= RED_BLOCKS && nwg <= cnn_device_cus() && cnn_barrier_words(s, &bar, &berr)) {
-    tail.gscale = gscale; tail.grads = a.grads; tail.loss = a.loss; tail.rng = a.rng; tail.params = a.params;
-    tail.hp = u.hp; tail.frag = static_cast<uint16_t*>(a.frag); tail.step = u.step; tail.bar = bar;
-    tail.err = berr; tail.accumulate = a.accumulate; tail.B = a.B; tail.on = 1;
-  }
-  // PDE_CNN_DIAG (timing diagnostics only, results invalid): 1 no reduce launch, 2 no train launch, 4 reduce
-  // slab-column roles only, 8 reduce fc1-tile roles only, 16 no SGD update / fragment refresh in the reduce
-  static const int diag = std::getenv("PDE_CNN_DIAG") ? std::atoi(std::getenv("PDE_CNN_DIAG")) : 0;
-  if (!(diag & 2))
-    hipLaunchKernelGGL(train, dim3(nwg), dim3(T), sm, s, a.images, a.tgt, a.B, a.params,
-                       static_cast<const u16x8*>(a.frag), a.rng, a.p_drop2, a.p_drop1, a.training, a.slabs,
-                       a.loss_part, a.acts, a.stamps, a.stop_after, tail, xmap);
-  if (!tail.on && !(diag & 1)) {
-    const int rb0 = (diag & 8) ? RED_SLAB_BLOCKS : 0;
-    const int nrb = (diag & 4) ? RED_SLAB_BLOCKS : (diag & 8) ? RED_BLOCKS - RED_SLAB_BLOCKS : RED_BLOCKS;
-    const float* hp = (diag & 16) ? nullptr : u.hp;
-    uint16_t* fr = static_cast<uint16_t*>(a.frag);
-    if (u.mode == CNN_SGD) {  // (no state arguments: k_cnn_reduce<0>'s pack is empty)
-      hipLaunchKernelGGL(k_cnn_reduce<0>, dim3(nrb), dim3(RED_T), 0, s, a.slabs, nwg, a.acts, gscale, a.grads,
-                         a.accumulate, a.loss_part, a.B, a.loss, a.rng, a.params, hp, fr, u.step, view, a.xscale,
-                         rb0);
-    } else {
-      using ReduceFn = decltype(&k_cnn_reduce<1, float*, float*>);
-      static const ReduceFn kReduce[3] = {&k_cnn_reduce<1, float*, float*>, &k_cnn_reduce<2, float*, float*>,
-                                          &k_cnn_reduce<3, float*, float*>};
-      hipLaunchKernelGGL(kReduce[u.mode - CNN_SGD_STATE], dim3(nrb), dim3(RED_T), 0, s, a.slabs, nwg, a.acts, gscale,
-                         a.grads, a.accumulate, a.loss_part, a.B, a.loss, a.rng, a.params, hp, fr, u.step, view,
-                         a.xscale, rb0, u.m, u.v);
-    }
+  hipLaunchKernelGGL(k_cnn_train, dim3(nwg), dim3(T), sm, s, a.images, a.tgt, a.B, a.params,
+                     static_cast<const u16x8*>(a.frag), a.rng, a.p_drop2, a.p_drop1, a.training, a.slabs,
+                     a.loss_part, a.acts, a.stamps, a.stop_after, cnn_p7b_fullk_enabled() ? 1 : 0);
+  uint16_t* fr = static_cast<uint16_t*>(a.frag);
+  if (u.mode == CNN_SGD) {  // (no state arguments: k_cnn_reduce<0>'s pack is empty)
+    hipLaunchKernelGGL(k_cnn_reduce<0>, dim3(RED_BLOCKS), dim3(RED_T), 0, s, a.slabs, nwg, a.acts, a.grads,
+                       a.accumulate, a.loss_part, a.B, a.loss, a.rng, a.params, u.hp, fr, u.step, view, a.xscale);
+  } else {
+    using ReduceFn = decltype(&k_cnn_reduce<1, float*, float*>);
+    static const ReduceFn kReduce[3] = {&k_cnn_reduce<1, float*, float*>, &k_cnn_reduce<2, float*, float*>,
+                                        &k_cnn_reduce<3, float*, float*>};
+    hipLaunchKernelGGL(kReduce[u.mode - CNN_SGD_STATE], dim3(RED_BLOCKS), dim3(RED_T), 0, s, a.slabs, nwg, a.acts,
+                       a.grads, a.accumulate, a.loss_part, a.B, a.loss, a.rng, a.params, u.hp, fr, u.step, view,
+                       a.xscale, u.m, u.v);
   }
   return hipGetLastError();
 }
