@@ -143,42 +143,70 @@ __host__ __device__ constexpr uint64_t p7b_pack(bool hi) {
 }
 constexpr uint64_t P7B_LO = p7b_pack(false), P7B_HI = p7b_pack(true);
 static_assert(KSD < 32 && MTD * 5 <= 64, "5-bit fields");
-// conv2 dgrad wave map: a wave runs the SAME class for two images (0, 1 or 2, 3), so both tiles share one B
-// fragment, one tap table entry and one bound check per k-step.  Classes 1..7 take two waves each; classes 0
-// and MTD - 1 (disjoint 7-step ranges) share the last two waves, which run class 0 and then class MTD - 1 for
-// their image pair.  Four waves share a SIMD's MFMA pipe (wave w on SIMD w % 4): the six 19-step waves and the
-// rest are dealt so that every SIMD carries 124-128 of the 504 tile-k-steps.
-constexpr int P7B_WCLS[NW] = {3, 4, 5, 5, 3, 4, 6, 6, 1, 7, 2, 2, 1, 7, 0, 0};
-constexpr int P7B_WPAIR[NW] = {0, 0, 0, 1, 1, 1, 0, 1, 0, 0, 0, 1, 1, 1, 0, 1};
-__host__ __device__ constexpr int p7b_wave_steps(int w) {  // tile-k-steps of wave w (two tiles per k-step)
+// conv2 backward wave map (P7).  Wave w runs on SIMD w % 4; waves 0 .. P7_DW - 1 take the data gradient, the other
+// P7_DW the weight gradient, so every SIMD carries two waves of each role and both roles run side by side from the
+// barrier after P6 to the one before P9.
+// dgrad: a wave runs ONE tile class for all NI images, so its four tiles share one B fragment, one tap table entry
+// and one bound check per k-step.  Classes 0 and MTD - 1 (disjoint 7-step ranges) share a wave, which runs class 0
+// and then class MTD - 1.  The two dgrad waves of a SIMD (w, w + 4) are paired long with short: every SIMD carries
+// 31-33 of the 126 k-steps (4 tiles each).
+// wgrad: a wave owns NT2 = 2 of the 16 N-tiles (kidx columns) for both M-tiles: it reads its two A fragments
+// once per k-step for both N-tiles.
+constexpr int P7_DW = 8;       // dgrad waves 0..7, wgrad waves 8..15
+constexpr int P7B_WCLS[P7_DW] = {3, 4, 5, 6, 1, 7, 0, 2};
+constexpr int NT2 = 16 / (NW - P7_DW);  // conv2-wgrad N-tiles (250 -> 16 x 16) per wgrad wave
+__host__ __device__ constexpr int p7a_tile(int w, int u) { return (w - P7_DW) * NT2 + u; }  // N-tile u of wave w
+__host__ __device__ constexpr int p7b_wave_steps(int w) {  // k-steps of dgrad wave w (NI tiles per k-step)
   const int c = P7B_WCLS[w];
   int n = p7b_ks_range(c).hi - p7b_ks_range(c).lo;
   if (c == 0) n += p7b_ks_range(MTD - 1).hi - p7b_ks_range(MTD - 1).lo;
-  return 2 * n;
+  return n;
 }
 __host__ __device__ constexpr bool p7b_map_ok() {
-  for (int c = 0; c < MTD - 1; ++c) {  // every (class, pair) on exactly one wave (class MTD - 1 rides with 0)
-    int n[2] = {0, 0};
-    for (int w = 0; w < NW; ++w)
-      if (P7B_WCLS[w] == c) ++n[P7B_WPAIR[w]];
-    if (n[0] != 1 || n[1] != 1) return false;
-  }
+  // every (class, image) on exactly one dgrad wave: a wave covers all NI images of its class, and class MTD - 1
+  // rides with class 0
+  for (int c = 0; c < MTD; ++c)
+    for (int im = 0; im < NI; ++im) {
+      int n = 0;
+      for (int w = 0; w < P7_DW; ++w)
+        if (P7B_WCLS[w] == (c == MTD - 1 ? 0 : c)) ++n;
+      if (n != 1) return false;
+    }
   int tot = 0;
-  for (int s = 0; s < 4; ++s) {
-    int n = 0;
-    for (int w = s; w < NW; w += 4) n += p7b_wave_steps(w);
-    if (n < 120 || n > 132) return false;
+  for (int s = 0; s < 4; ++s) {  // a SIMD's dgrad k-steps inside the band, two waves of each role on it
+    int n = 0, nd = 0, nw = 0;
+    for (int w = s; w < NW; w += 4) {
+      if (w < P7_DW) {
+        n += p7b_wave_steps(w);
+        ++nd;
+      } else {
+        ++nw;
+      }
+    }
+    if (n < 31 || n > 33 || nd != 2 || nw != 2) return false;
     tot += n;
   }
-  return tot == NI * 126;
+  return tot == 126;
+}
+__host__ __device__ constexpr bool p7a_map_ok() {  // every (N-tile, M-tile) on exactly one wgrad wave
+  for (int nt = 0; nt < 16; ++nt)
+    for (int mt = 0; mt < 2; ++mt) {  // a wave runs both M-tiles of its N-tiles
+      int n = 0;
+      for (int w = P7_DW; w < NW; ++w)
+        for (int u = 0; u < NT2; ++u)
+          if (p7a_tile(w, u) == nt) ++n;
+      if (n != 1) return false;
+    }
+  return true;
 }
 static_assert(NW == 16 && NI == 4 && p7b_map_ok(), "conv2 dgrad wave map: complete, balanced over the SIMDs");
-__host__ __device__ constexpr uint64_t p7b_pack_map(bool pair) {
+static_assert(NT2 == 2 && NT2 * (NW - P7_DW) == 16 && p7a_map_ok(), "conv2 wgrad wave map: complete");
+__host__ __device__ constexpr uint64_t p7b_pack_map() {
   uint64_t v = 0;
-  for (int w = 0; w < NW; ++w) v |= static_cast<uint64_t>(pair ? P7B_WPAIR[w] : P7B_WCLS[w]) << (4 * w);
+  for (int w = 0; w < P7_DW; ++w) v |= static_cast<uint64_t>(P7B_WCLS[w]) << (4 * w);
   return v;
 }
-constexpr uint64_t P7B_MCLS = p7b_pack_map(false), P7B_MPAIR = p7b_pack_map(true);
+constexpr uint64_t P7B_MCLS = p7b_pack_map();
 // parameter offsets in the flat gradient (torch parameter order of Net)
 constexpr int O_W1 = 0, O_B1 = O_W1 + W1N, O_W2 = O_B1 + C1, O_B2 = O_W2 + W2N, O_FC1W = O_B2 + C2,
               O_FC1B = O_FC1W + FC1N, O_FC2W = O_FC1B + F1, O_FC2B = O_FC2W + FC2N, NPARAM = O_FC2B + F2;
@@ -290,7 +318,6 @@ static_assert(offsetof(CnnSmem, d2n) == offsetof(CnnSmem, w1f) + sizeof(u16x8) *
                   NW * 2 * 64 * sizeof(f32x4) <= sizeof(u16x8) * (KSD * 64 + 64) + sizeof(uint16_t) * NI * D2N_IM,
               "P9 partials alias w2d + w1f + d2n (not e1)");
 static_assert(offsetof(CnnSmem, w2d) == offsetof(CnnSmem, w2f) + sizeof(u16x8) * KS2 * 2 * 64, "w2f, w2d adjacent");
-constexpr int NT2 = 16 / NW;  // conv2-wgrad N-tiles (250 -> 16 x 16) per wave
 constexpr int NFRAG = KS2 * 2 * 64 + KSD * 64 + 64;  // bf16 MFMA weight fragments (w2f, w2d, w1f)
 constexpr int NF2F = KS2 * 2 * 64, NF2D = KSD * 64;  // fragment image: [w2f | w2d | w1f]
 static_assert(NF2F <= 2 * T && NF2D <= 2 * T && NF2F + NF2D + 64 == NFRAG, "fragment slots");
@@ -304,7 +331,6 @@ constexpr int DP2_J = 16;               // rows per chunk (the last one takes th
 static_assert(F1 - DP2_J * (DP2_JC - 1) <= 20 && DP2_J % 4 == 0 && DHP >= DP2_J * (DP2_JC - 1) + 20, "dp2 chunks");
 static_assert(F1 * FC1_KC <= T && NIN * DP2_JC <= T, "fc1 work split");
 static_assert(sizeof(float) * NI * NIN * DP2_JC <= sizeof(u16x8) * KS2 * 2 * 64, "dp2 partials alias w2f");
-static_assert(NT2 * NW == 16, "conv2 wgrad tiling");
 
 // Workgroup barrier for LDS hand-offs only: every wave's LDS accesses complete (lgkmcnt), then s_barrier --
 // outstanding GLOBAL loads and stores stay in flight (an LDS-scoped fence; __syncthreads would also wait
@@ -985,20 +1011,29 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
   }
   lds_sync();
   PDE_STAMP(8);
-  if (t >= 448 && t < 448 + C2) {  // conv2 bias gradient (dp2 is not overwritten before P9)
-    const int co = t - 448;
-    f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int im = 0; im < NI; ++im)
-#pragma unroll
-      for (int c = 0; c < NC2; c += 4) s4 += *reinterpret_cast<const f32x4*>(&S.dp2[im][co * NC2 + c]);
-    out_st(&slab[O_B2 + co], (s4[0] + s4[1]) + (s4[2] + s4[3]));
-  }
-
+  // ---- P7: conv2's backward, both gradients side by side from this barrier to the one before P9: waves P7_DW..
+  // run the weight gradient (P7a), waves 0 .. P7_DW - 1 the data gradient (P7b) -- wave-uniform scalar branches
+  // on wid, two waves of each role on every SIMD (the wave map above).
   // ---- P7a: conv2 wgrad (MFMA): dW2[co][(ci,ky,kx)] = sum_(im,y,x) d2[co][y][x] * r1[ci][y+ky][x+kx].
   // M = co (2 tiles), N = 250 -> 16 tiles (NT2 per wave), K = (im, y, x) 256 = 8 k-steps.  An A fragment
-  // is one 16-byte row of the d2 plane.
-  {
+  // is one 16-byte row of the d2 plane, read once per k-step for the wave's NT2 N-tiles.
+  if (wid >= P7_DW) {
+    // Raised issue priority until the slab stores are out: the wgrad waves have the short job (8 k-steps), and
+    // their write-through stores should leave early, to drain under the dgrad.  At equal priority they finish
+    // late: the 8 -> 10 span is the same, but P9 runs 0.2-0.3 us longer and the kernel's end waits 0.6 us more
+    // for the stores (profiles/cnn_p7_wave_roles.md)
+    __builtin_amdgcn_s_setprio(3);
+    constexpr int TB2 = (NW - 1) * 64;  // conv2 bias gradient: the first C2 lanes of the last wgrad wave
+    static_assert(C2 <= 64 && NW - 1 >= P7_DW, "conv2 bias gradient on a wgrad wave");
+    if (t >= TB2 && t < TB2 + C2) {  // (dp2 is not overwritten before P9)
+      const int co = t - TB2;
+      f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int im = 0; im < NI; ++im)
+#pragma unroll
+        for (int c = 0; c < NC2; c += 4) s4 += *reinterpret_cast<const f32x4*>(&S.dp2[im][co * NC2 + c]);
+      out_st(&slab[O_B2 + co], (s4[0] + s4[1]) + (s4[2] + s4[3]));
+    }
     // B gathers: the 8 consecutive u16 of a fragment start at a 2-byte-aligned address, so they are read as the
     // 5 aligned words covering them and funnel-shifted (v_alignbyte) when the start is odd -- one 16-byte read
     // there would be an unaligned LDS access (64 cycles), 8 masked u16 reads cost an exec round trip each
@@ -1007,7 +1042,7 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
     int nb[NT2];
 #pragma unroll
     for (int u = 0; u < NT2; ++u) {
-      const int kidx = (wid * NT2 + u) * 16 + lr, ci = kidx / 25, r = kidx - ci * 25, ky = r / 5, kx = r - ky * 5;
+      const int kidx = p7a_tile(wid, u) * 16 + lr, ci = kidx / 25, r = kidx - ci * 25, ky = r / 5, kx = r - ky * 5;
       nb[u] = kidx < K2 ? ci * RP16 + ky * P1 + kx : 0;
     }
     const uint16_t* arow[2];
@@ -1046,29 +1081,27 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int u = 0; u < NT2; ++u) {
-        const int kidx = (wid * NT2 + u) * 16 + lr, cg = mt * 4 + lg;
+        const int kidx = p7a_tile(wid, u) * 16 + lr, cg = mt * 4 + lg;
         if (cg * 4 < C2 && kidx < K2) out_st4(&slab[O_W2 + (cg * K2 + kidx) * 4], acc[mt][u]);
       }
-  }
-  PDE_STAMP(9);
-
-  // ---- P7b: conv2 dgrad (MFMA): dr1[ci][Y][X] = sum_(ky,kx) sum_co d2[Y-ky][X-kx][co] * w2[co][ci][ky][kx],
-  // then relu'(r1).  M = r1 positions (9 tiles per image, 36 total), N = ci, K = (tap, co24) packed into 19
-  // k-steps: a lane's A fragment is the 16-byte co-group of ITS tap's source position (Y-ky, X-kx), or the zero
-  // block when that position lies outside the 8x8 conv2 output -- every read is unconditional, so the k-loop
-  // pipelines its LDS reads ahead of the MFMAs.  A wave owns one tile class for two images (P7B_WCLS): its two
-  // tiles cover the same positions, so they share the B fragment, the tap entry and the bound check of a k-step,
-  // and the k-loop runs only the class's k-steps (p7b_ks_range: the others add exact zeros, so the sums keep
-  // their bits).  The phase is bound by LDS fragment reads and VALU issue, both per (tile, k-step).
-  {
-    constexpr int MAXT = 2;
+    __builtin_amdgcn_s_setprio(0);
+  } else {
+    // ---- P7b: conv2 dgrad (MFMA): dr1[ci][Y][X] = sum_(ky,kx) sum_co d2[Y-ky][X-kx][co] * w2[co][ci][ky][kx],
+    // then relu'(r1).  M = r1 positions (9 tiles per image, 36 total), N = ci, K = (tap, co24) packed into 19
+    // k-steps: a lane's A fragment is the 16-byte co-group of ITS tap's source position (Y-ky, X-kx), or the zero
+    // block when that position lies outside the 8x8 conv2 output -- every read is unconditional, so the k-loop
+    // pipelines its LDS reads ahead of the MFMAs.  A wave owns one tile class for all NI images (P7B_WCLS): its
+    // four tiles cover the same positions, so they share the B fragment, the tap entry and the bound check of a
+    // k-step, and the k-loop runs only the class's k-steps (p7b_ks_range: the others add exact zeros, so the sums
+    // keep their bits).  Each tile has its own accumulator, summed over ascending k-steps.
+    constexpr int MAXT = NI;
     const int cls0 = static_cast<int>(P7B_MCLS >> (4 * wid)) & 15;            // wave-uniform, scalar
-    const int im0 = (static_cast<int>(P7B_MPAIR >> (4 * wid)) & 1) * MAXT;    // images im0, im0 + 1
-    const int npass = cls0 == 0 ? 2 : 1;  // the class-0 waves go on with class MTD - 1
+    constexpr int im0 = 0;                                                    // images 0 .. NI - 1
+    const int npass = cls0 == 0 ? 2 : 1;  // the class-0 wave goes on with class MTD - 1
     // LDS addresses as 32-bit offsets (the A reads select between two of them)
     const uint32_t sbase = lds_addr(smem_raw);
     const uint32_t zpo = sbase + static_cast<uint32_t>(offsetof(CnnSmem, zero16));  // the zero block
-    constexpr uint32_t IMB = D2N_IM * 2;  // bytes between the two images' slots
+    constexpr uint32_t IMB = D2N_IM * 2;  // bytes between two images' slots
     // e1 aliases r1n / w2f, which no P7a / P7b wave reads (r1 itself is still P7a's B operand: no barrier here)
     uint32_t* e1 = reinterpret_cast<uint32_t*>(&S.r1n[0][0][0]);
     auto run_pass = [&](int pass) {
@@ -1165,6 +1198,7 @@ __global__ __launch_bounds__(T) void k_cnn_train(const float* __restrict__ image
     };
     for (int pass = 0; pass < npass; ++pass) run_pass(pass);
   }
+  PDE_STAMP(9);  // wave 0 (a dgrad wave) finished its P7 role
   lds_sync();
   PDE_STAMP(10);
 

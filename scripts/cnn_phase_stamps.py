@@ -31,6 +31,9 @@ print("P1 conv1 MFMA part (stamp 1 -> 13) median", ((st[:, 13] - st[:, 1]) / 100
       "fragment wait + stores (13 -> 2)", ((st[:, 2] - st[:, 13]) / 100.0).median().item(), "us")
 print("P1 conv1 MFMA part by wave: 0 / 15 median",
       [round(((st[:, k] - st[:, 1]) / 100.0).median().item(), 2) for k in (13, 15)], "us")
+# P7a / P7b run side by side on separate waves: stamp 9 is "wave 0 (a dgrad wave) finished its role", so the two
+# rows above are wave 0's dgrad time and its wait at the barrier -- compare the 8 -> 10 span
+print("P7 conv2 backward, both roles (8 -> 10) median", ((st[:, 10] - st[:, 8]) / 100.0).median().item(), "us")
 print("P9 split: loads + MFMAs + partials (10 -> 14)", ((st[:, 14] - st[:, 10]) / 100.0).median().item(),
       "us; combine + stores (14 -> 11)", ((st[:, 11] - st[:, 14]) / 100.0).median().item(), "us")
 print("total median", (st[:, 11] - st[:, 0]).median().item() / 100.0, "us")
