@@ -15,6 +15,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "mlp_eval.h"
 #include "mlp_train.h"
 #include "pde_kernels.h"
 
@@ -1461,6 +1462,72 @@ void mlp_train(const Tensor& x, const Tensor& y, const std::vector<Tensor>& w, c
   check(pde::mlp_train_step(a, grid, cur_stream()), "mlp_train");
 }
 
+// Forward-only evaluation of a Linear(+ReLU) stack in one launch (k_mlp_eval): (pred, logits, logp), each an
+// undefined tensor when not asked for.  w: the layers' bf16 weight copies [out][in], b: their fp32 biases.  stats: a
+// CnnEvalStats buffer (int64[4]) the batch's NLL sum / correct / count are added to; it needs the labels and
+// part, a float workspace of at least ceil(B / mlp_eval_rows_per_workgroup()) elements the caller keeps (so a call
+// neither allocates it nor synchronises).
+std::tuple<Tensor, Tensor, Tensor> mlp_eval(const Tensor& x, const optional<Tensor>& tgt, const std::vector<Tensor>& w,
+                                            const std::vector<Tensor>& b, bool want_pred, bool want_logits,
+                                            bool want_logp, const optional<Tensor>& stats,
+                                            const optional<Tensor>& part) {
+  const int nl = static_cast<int>(w.size());
+  TORCH_CHECK(nl >= 2 && nl <= pde::kMlpMaxLayers, "mlp_eval: 2 <= layers <= ", pde::kMlpMaxLayers, ", got ", nl);
+  TORCH_CHECK(b.size() == w.size(), "mlp_eval: one bias per layer");
+  CHECK_IN(x); CHECK_F32(x);
+  TORCH_CHECK(x.dim() == 2 && x.size(0) >= 1, "mlp_eval: x must be [B, in] with B >= 1");
+  TORCH_CHECK(x.size(0) <= (1 << 30), "mlp_eval: batch too large");
+  const int B = static_cast<int>(x.size(0));
+  pde::MlpEvalArgs a{};
+  a.nl = nl; a.B = B;
+  for (int l = 0; l < nl; ++l) {
+    const bool last = l == nl - 1;
+    CHECK_IN(w[l]); CHECK_BF16(w[l]); CHECK_IN(b[l]); CHECK_F32(b[l]);
+    TORCH_CHECK(w[l].dim() == 2 && b[l].numel() == w[l].size(0), "mlp_eval: layer ", l, ": w [out][in], b [out]");
+    const int64_t in = w[l].size(1), out = w[l].size(0);
+    TORCH_CHECK(in == (l == 0 ? x.size(1) : w[l - 1].size(0)), "mlp_eval: layer ", l, " reads ", in, " features");
+    TORCH_CHECK(in >= 8 && in % 8 == 0 && in <= 1024, "mlp_eval: layer ", l,
+                ": in must be a multiple of 8 and at most 1024, got ", in);
+    if (last) {
+      TORCH_CHECK(out >= 1 && out <= 16, "mlp_eval: the last layer's out must be at most 16, got ", out);
+    } else {
+      TORCH_CHECK(out >= 8 && out % 8 == 0 && out <= 1024, "mlp_eval: layer ", l,
+                  ": a hidden out must be a multiple of 8 and at most 1024, got ", out);
+    }
+    a.L[l].w = reinterpret_cast<const uint16_t*>(w[l].data_ptr());
+    a.L[l].b = b[l].data_ptr<float>();
+    a.L[l].in = static_cast<int>(in); a.L[l].out = static_cast<int>(out);
+  }
+  const int nout = a.L[nl - 1].out;
+  const bool have_tgt = tgt.has_value() && tgt->defined();
+  if (have_tgt) {
+    CHECK_IN(*tgt);
+    TORCH_CHECK(tgt->scalar_type() == at::kLong && tgt->numel() == B, "mlp_eval: tgt must be int64 [B]");
+    a.tgt = tgt->data_ptr<int64_t>();
+  }
+  if (stats.has_value() && stats->defined()) {
+    CHECK_IN(*stats);
+    TORCH_CHECK(have_tgt, "mlp_eval: stats need the labels");
+    TORCH_CHECK(stats->scalar_type() == at::kLong && stats->numel() == 4, "mlp_eval: stats must be int64[4]");
+    TORCH_CHECK(part.has_value() && part->defined(), "mlp_eval: stats need the partials workspace");
+    CHECK_IN(*part); CHECK_F32(*part);
+    const int rows = pde::mlp_eval_rows_per_workgroup();
+    TORCH_CHECK(part->numel() >= (B + rows - 1) / rows, "mlp_eval: part holds one float per workgroup");
+    a.stats = stats->data_ptr();
+    a.loss_part = part->data_ptr<float>();
+  }
+  a.x = x.data_ptr<float>();
+  Tensor pred, logits, logp;
+  if (want_pred) pred = at::empty({B}, x.options().dtype(at::kLong));
+  if (want_logits) logits = at::empty({B, nout}, x.options());
+  if (want_logp) logp = at::empty({B, nout}, x.options());
+  a.pred = want_pred ? pred.data_ptr<int64_t>() : nullptr;
+  a.logits = want_logits ? logits.data_ptr<float>() : nullptr;
+  a.logp = want_logp ? logp.data_ptr<float>() : nullptr;
+  check(pde::mlp_eval(a, cur_stream()), "mlp_eval");
+  return std::make_tuple(pred, logits, logp);
+}
+
 // The update of `mode` over the flat CNN parameters + the fragment-image refresh, ONE launch, after a gradient
 // all-reduce that ran outside the reduction kernel (FusedCNN.opt_step).  step may be None for plain SGD.
 void cnn_opt(Tensor& params, const Tensor& grads, Tensor& frag, const Tensor& hp, const optional<Tensor>& step,
@@ -1553,6 +1620,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cnn_eval", &cnn_eval, py::arg("images"), py::arg("tgt"), py::arg("params"), py::arg("frag"),
         py::arg("prep"), py::arg("want_pred") = true, py::arg("want_logp") = false, py::arg("stats") = py::none());
   m.def("cnn_eval_images_per_workgroup", &pde::cnn_eval_images_per_workgroup);
+  m.def("mlp_eval", &mlp_eval, py::arg("x"), py::arg("tgt"), py::arg("w"), py::arg("b"), py::arg("want_pred") = true,
+        py::arg("want_logits") = false, py::arg("want_logp") = false, py::arg("stats") = py::none(),
+        py::arg("part") = py::none());
+  m.def("mlp_eval_rows_per_workgroup", &pde::mlp_eval_rows_per_workgroup);
   m.def("cnn_frag_bytes", &pde::cnn_frag_bytes);
   m.def("cnn_num_params", &pde::cnn_num_params);
   m.def("cnn_smem_bytes", &pde::cnn_smem_bytes);

@@ -29,7 +29,7 @@ EXTENSIONS = {
     "_C": (
         ["kernels/gemm.hip", "kernels/gemm_dma_tt.hip", "kernels/gemm_dma_tf.hip", "kernels/gemm_dma_ft.hip",
          "kernels/gemm_dma_ff.hip", "kernels/gemm_dma_pair.hip", "kernels/elementwise.hip", "kernels/loss.hip", "kernels/optim.hip",
-         "kernels/norm_pool.hip", "kernels/cnn_fused.hip", "kernels/mlp_fused.hip"],
+         "kernels/norm_pool.hip", "kernels/cnn_fused.hip", "kernels/mlp_fused.hip", "kernels/mlp_eval.hip"],
         ["bindings.cpp"],
     ),
     "_comm": (
@@ -45,6 +45,8 @@ EXTENSIONS = {
 # (The host compiler ignores the device target feature with a warning.)
 HIP_FLAGS = {
     "kernels/cnn_fused.hip": ["-Xclang", "-target-feature", "-Xclang", "-unaligned-access-mode"],
+    # mlp_eval.hip keeps its fp32 epilogue and head on the scalar-per-lane VALU forms (no packed fp32 pairs)
+    "kernels/mlp_eval.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 # GEMM ring depth / K-tiles per barrier / DMA ring slots / default core sweeps (gemm_common.h / gemm_ring.h / gemm_dma.h)
 _GEMM_SRCS = ("kernels/gemm.hip", "kernels/gemm_dma_tt.hip", "kernels/gemm_dma_tf.hip", "kernels/gemm_dma_ft.hip",

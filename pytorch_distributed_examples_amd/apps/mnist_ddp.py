@@ -275,6 +275,11 @@ class Trainer:
                 self.fused.evaluate(images, labels, stats)
                 total += labels.size(0)
             c = stats.result()[1]
+        elif type(self.model).__name__ == "MLP" and self.ctx.device.type == "cuda":
+            # --model mlp: one k_mlp_eval launch per chunk of the shard (PDE_MLP_EVAL=0: it runs this layer pass itself)
+            from ..models.mlp_eval import mlp_eval_pass
+
+            c, total, _ = mlp_eval_pass(self.model, self.test_data, self.ctx.device)
         else:
             correct = torch.zeros((), dtype=torch.long, device=self.ctx.device)
             for images, labels in self.test_data:

@@ -578,6 +578,11 @@ def _test(model, loader, dev, comm, log, fused=None):
             fused.evaluate(images, labels, stats)
             total += labels.size(0)
         correct = stats.result()[1]
+    elif type(model).__name__ == "MLP" and torch.device(dev).type == "cuda":
+        # --model mlp: one k_mlp_eval launch per chunk of the shard (PDE_MLP_EVAL=0: it runs this layer pass itself)
+        from ..models.mlp_eval import mlp_eval_pass
+
+        correct, total, _ = mlp_eval_pass(model, loader, dev)
     else:
         count = torch.zeros((), dtype=torch.long, device=dev)
         for images, labels in loader:

@@ -5,7 +5,9 @@ Same module / parameter names as the reference ``Model`` (``input_layer``, ``hid
 ``final_layer``) so its ``MODEL_STATE`` snapshots load unchanged.  On GPU every layer is one bf16 MFMA
 GEMM with bias + ReLU fused in the epilogue; in backward each layer's dgrad GEMM applies the ReLU mask of
 its producer in the epilogue (threshold_backward fused), the final layer emits fp32 logits for the fused
-cross-entropy kernel.
+cross-entropy kernel.  Evaluation has a path of its own: :class:`.mlp_eval.FusedMLPEval` runs the whole
+stack, log-softmax, argmax and the test pass's totals in one launch (``k_mlp_eval``), reading the same bf16 weight
+copies as ``forward``.
 """
 from __future__ import annotations
 
