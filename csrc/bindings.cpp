@@ -957,6 +957,43 @@ void optim_step(const Tensor& table, const Tensor& chunks, int64_t nchunks, int 
         "optim_step");
 }
 
+// Trust-ratio optimisers (optim_trust.hip): next to optim_table's (table, chunks) the per-tensor chunk spans -- the
+// same cut, in the same order -- and the float2[nchunks] norm workspace.  Returns (spans, norms, nchunks).
+std::tuple<Tensor, Tensor, int64_t> optim_trust_table(const std::vector<Tensor>& params) {
+  TORCH_CHECK(!params.empty(), "optim_trust_table: no parameters");
+  const long chunk = pde::optim_chunk_elems();
+  std::vector<pde::TrustSpan> spans(params.size());
+  long c = 0;
+  for (size_t i = 0; i < params.size(); ++i) {
+    const long nc = (params[i].numel() + chunk - 1) / chunk;
+    TORCH_CHECK(c + nc < (1L << 31), "optim_trust_table: too many chunks");
+    spans[i] = pde::TrustSpan{static_cast<int>(c), static_cast<int>(nc)};
+    c += nc;
+  }
+  auto opts = params[0].options();
+  Tensor dspans = to_device_bytes(spans.data(), static_cast<long>(spans.size() * sizeof(pde::TrustSpan)), opts);
+  Tensor norms = at::zeros({std::max<long>(c, 1), 2}, opts.dtype(at::kFloat));
+  return {dspans, norms, static_cast<int64_t>(c)};
+}
+
+void optim_trust_step(const Tensor& table, const Tensor& chunks, int64_t nchunks, const Tensor& spans,
+                      Tensor& norms, int kind, const Tensor& hparams, Tensor& step) {
+  CHECK_IN(table); CHECK_IN(chunks); CHECK_IN(spans); CHECK_IN(norms); CHECK_IN(hparams); CHECK_IN(step);
+  CHECK_F32(norms);
+  TORCH_CHECK(hparams.numel() >= pde::HP_COUNT, "hparams size");
+  TORCH_CHECK(step.scalar_type() == at::kInt && step.numel() >= 2, "step must be int32[2]");
+  const long ntensors = static_cast<long>(table.nbytes() / sizeof(pde::OptimEntry));
+  TORCH_CHECK(nchunks >= 0 && chunks.nbytes() == static_cast<size_t>(nchunks) * sizeof(pde::OptimChunk) &&
+                  norms.numel() >= 2 * nchunks && spans.nbytes() == static_cast<size_t>(ntensors) * sizeof(pde::TrustSpan),
+              "optim_trust_step: the tables are not those of one optim_table / optim_trust_table pair");
+  check(pde::multi_tensor_trust(kind, reinterpret_cast<const pde::OptimEntry*>(table.data_ptr()),
+                                reinterpret_cast<const pde::OptimChunk*>(chunks.data_ptr()),
+                                static_cast<int>(nchunks), reinterpret_cast<const pde::TrustSpan*>(spans.data_ptr()),
+                                norms.data_ptr<float>(), hparams.data_ptr<float>(), step.data_ptr<int>(),
+                                cur_stream()),
+        "optim_trust_step");
+}
+
 // Chunk range [c0, c1) of an optimiser table: its own launch (publish: the step's last segment advances the
 // device step counter), or -- optim_attach -- appended as extra blocks to the NEXT paired GEMM launch
 // (gemm_pair_end), so the HBM-bound update of one layer overlaps the latency-bound backward GEMMs of the next.
@@ -1700,6 +1737,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mse_bwd", &mse_bwd);
   m.def("optim_table", &optim_table);
   m.def("optim_step", &optim_step);
+  m.def("optim_trust_table", &optim_trust_table);
+  m.def("optim_trust_step", &optim_trust_step);
   m.def("optim_step_range", &optim_step_range);
   m.def("optim_chunk_elems", &pde::optim_chunk_elems);
   m.def("optim_attach", &optim_attach);

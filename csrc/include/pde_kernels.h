@@ -240,6 +240,18 @@ hipError_t multi_tensor_optim_range(int mode, const OptimEntry* dev_table, const
 hipError_t multi_tensor_optim(int mode, const OptimEntry* dev_table, const OptimChunk* dev_chunks, int nchunks,
                               const float* dev_hparams, int* dev_step, hipStream_t s);
 
+// Trust-ratio optimisers (optim_trust.hip): kind 0 LAMB, 1 LARS, over the same table in TWO launches -- the chunks'
+// squared norms (dev_norms: float2[nchunks], written before it is read, never allocated per step), then the update
+// with each tensor's ratio.  dev_spans[tensor]: the tensor's chunks [c0, c0 + nc) of the chunk list.  LARS reads its
+// trust coefficient from HP_TRUST, the slot of beta1.  hipErrorInvalidValue on a bad kind or a null pointer.
+struct TrustSpan {
+  int c0, nc;
+};
+constexpr int HP_TRUST = HP_BETA1;
+hipError_t multi_tensor_trust(int kind, const OptimEntry* dev_table, const OptimChunk* dev_chunks, int nchunks,
+                              const TrustSpan* dev_spans, float* dev_norms, const float* dev_hparams, int* dev_step,
+                              hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------
 // BatchNorm / pooling / dropout / EmbeddingBag (norm_pool.hip).  Activations NHWC bf16, [P = N*H*W][C].
 // ---------------------------------------------------------------------------------------------

@@ -43,7 +43,7 @@ from ..data.mnist import mnist_datasets
 from ..elastic import fault
 from ..elastic.snapshot import load_snapshot, save_snapshot
 from ..ops import functional as OF
-from ..ops.optim import FusedAdam, FusedSGD
+from ..ops.optim import _MODES, FusedAdam, FusedLAMB, FusedLARS, FusedSGD
 from ..parallel import dist as pdist
 from ..parallel.ddp import DistributedDataParallel
 from ..utils.log import RankLogger, MetricsWriter
@@ -52,8 +52,11 @@ from ..utils.config import add_runtime_args
 
 
 def load_train_objs(model_name: str, device, train_size: int, test_size: int, data_dir=None,
-                    momentum: float = 0.0, weight_decay: float = 0.0):
+                    momentum: float = 0.0, weight_decay: float = 0.0, optimizer: str | None = None):
     train_set, test_set = mnist_datasets(device, train_size, test_size, data_dir)
+    allowed = ("sgd", "lars") if model_name == "cnn" else ("adam", "lamb")
+    if optimizer is not None and optimizer not in allowed:
+        raise SystemExit(f"--model {model_name} takes --optimizer {' or '.join(allowed)}, not {optimizer}")
     if model_name == "cnn":
         from ..models.cnn import Net
 
@@ -62,12 +65,18 @@ def load_train_objs(model_name: str, device, train_size: int, test_size: int, da
         # (mnist_horovod.py:50 is plain SGD; --momentum / --weight_decay: the fused step applies those too)
         make_opt = lambda params: FusedSGD(params, lr=0.01, momentum=momentum,  # noqa: E731
                                            weight_decay=weight_decay)
+        if optimizer == "lars":
+            # the large-batch rule: the layer-wise ratio (trust coefficient 1e-3) carries a base rate near 1
+            make_opt = lambda params: FusedLARS(params, lr=1.0, momentum=momentum or 0.9,  # noqa: E731
+                                                weight_decay=weight_decay)
     else:
         from ..models.mlp import reference_mlp
 
         model = reference_mlp()
         loss = OF.cross_entropy
         make_opt = lambda params: FusedAdam(params, lr=1e-3)  # noqa: E731  (mnist_ddp_elastic.py:173)
+        if optimizer == "lamb":
+            make_opt = lambda params: FusedLAMB(params, lr=1e-3)  # noqa: E731
     return train_set, test_set, model, make_opt, loss
 
 
@@ -126,7 +135,9 @@ class Trainer:
             world = self.ddp.world
             own_gpu = torch.cuda.device_count() >= int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
             single_node = int(os.environ.get("LOCAL_WORLD_SIZE", str(world))) == world
+            # (the one-launch step applies the update itself: only the kinds it knows, _MODES)
             if (train_data.batch_size % 32 == 0 and os.environ.get("PDE_MLP_MEGA", "1") != "0" and
+                    getattr(self.optimizer, "KIND", "") in _MODES and
                     (world == 1 or (own_gpu and single_node and getattr(self.optimizer, "KIND", "") != "sgd"))):
                 from ..models.mlp_mega import MegaMLP
 
@@ -185,7 +196,14 @@ class Trainer:
             self.global_step += 1
 
     def _fused_cnn_step(self, source, targets):
+        from ..models.cnn_fused import fused_update_mode
+
         xgmi = getattr(self.ddp.comm, "xgmi", None)
+        if fused_update_mode(self.optimizer) is None:  # FusedLARS: its own two-launch step behind the all-reduce
+            loss = self.fused.forward_backward(source, targets, grad_out=self.ddp.flat_grad)
+            self.ddp.sync_gradients()
+            self.optimizer.step()
+            return loss
         if self.ddp.world == 1 or xgmi is not None:
             # SGD (+ momentum / weight decay) + fragment refresh inside the slab reduction, which at world > 1 also
             # exchanges the gradients over xGMI (an xgmi of size 1 is ignored)
@@ -304,6 +322,9 @@ def build_parser():
     parser.add_argument("--momentum", type=float, default=0.0, help="--model cnn: SGD momentum (default: 0)")
     parser.add_argument("--weight_decay", type=float, default=0.0,
                         help="--model cnn: SGD L2 weight decay (default: 0)")
+    parser.add_argument("--optimizer", default=None, choices=["adam", "lamb", "sgd", "lars"],
+                        help="mlp: adam (default) or lamb; cnn: sgd (default) or lars -- the trust-ratio optimisers "
+                             "of ops/optim.py (two launches per step)")
     parser.add_argument("--fused", action="store_true",
                         help="cnn: whole-network fused training kernel (GPU; the default GPU path, kept for scripts)")
     parser.add_argument("--layers", action="store_true",
@@ -331,6 +352,8 @@ def main(argv=None):
     args.device = rtconfig.device_for(cfg, args.device)
 
     start = time.time()
+    if args.rewire and args.optimizer in ("lamb", "lars"):
+        raise SystemExit("--rewire keeps the default optimisers: --optimizer lamb / lars is not wired into it")
     if args.rewire and args.fused and args.model == "cnn":
         # the fused whole-step CNN with the gradient exchange over xGMI inside its reduction kernel, one hipGraph
         # per membership round (BASELINE config 2's data plane; CPU: the same protocol over autograd + gloo)
@@ -347,7 +370,8 @@ def main(argv=None):
         metrics = MetricsWriter(args.metrics) if args.metrics and ctx.rank == 0 else None
         train_set, test_set, model, make_opt, criterion = load_train_objs(args.model, ctx.device, args.train_size,
                                                                           args.test_size, args.data_dir,
-                                                                          args.momentum, args.weight_decay)
+                                                                          args.momentum, args.weight_decay,
+                                                                          args.optimizer)
         train_data = ShardedLoader(train_set, args.batch_size, ctx.world_size, ctx.rank, shuffle=True)
         test_data = ShardedLoader(test_set, args.batch_size, ctx.world_size, ctx.rank, shuffle=False)
         trainer = Trainer(ctx, model, train_data, test_data, make_opt, criterion, args.save_every,

@@ -28,7 +28,7 @@ from ..data.loader import ShardedLoader
 from ..data.mnist import mnist_datasets
 from ..models.cnn import Net
 from ..ops import functional as OF
-from ..ops.optim import FusedSGD
+from ..ops.optim import FusedLARS, FusedSGD
 from ..parallel import dist as pdist
 from ..utils.epoch_graph import AsyncLossLog
 from ..utils import config as rtconfig
@@ -39,9 +39,12 @@ def build_parser():
     ap = argparse.ArgumentParser(description="Horovod-style MNIST CNN")
     ap.add_argument("--epochs", type=int, default=50)
     ap.add_argument("--batch-size", type=int, default=1024)
-    ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--lr", type=float, default=None,
+                    help="default: 0.01 (sgd); 1.0 (lars: the trust coefficient 1e-3 scales every layer's rate)")
     ap.add_argument("--momentum", type=float, default=0.0, help="SGD momentum (default: 0, the reference)")
     ap.add_argument("--weight-decay", type=float, default=0.0, help="SGD L2 weight decay (default: 0)")
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
+                    help="lars: ops/optim.py FusedLARS, momentum 0.9 unless --momentum is given (two launches per step)")
     ap.add_argument("--train-size", type=int, default=60000)
     ap.add_argument("--data-dir", default=None,
                     help="directory with the four MNIST IDX files (plain or .gz; also DIR/MNIST/raw, DIR/raw); never "
@@ -73,7 +76,13 @@ def main(argv=None):
 
     model = Net().to(dev)
     fast = dev.type == "cuda" and not args.layers
-    optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
+    if args.lr is None:
+        args.lr = 1.0 if args.optimizer == "lars" else 0.01
+    if args.optimizer == "lars":
+        optimizer = FusedLARS(model.parameters(), lr=args.lr, momentum=args.momentum or 0.9,
+                              weight_decay=args.weight_decay)
+    else:
+        optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
     if args.use_adasum:  # (FusedHvdStep: the fused kernel's local gradients + the two Adasum launches on the deltas)
         optimizer = hvd.DistributedOptimizer(optimizer, named_parameters=model.named_parameters(),
                                              compression=getattr(hvd.Compression, args.compression), op=hvd.Adasum)

@@ -1,4 +1,4 @@
-"""Fused multi-tensor optimisers: SGD, Adam, AdamW.
+"""Fused multi-tensor optimisers: SGD, Adam, AdamW, and the trust-ratio pair LAMB and LARS.
 
 GPU parameters are updated by ONE ``multi_tensor_optim`` launch per param group (csrc/kernels/optim.hip)
 whose hyper-parameters and step counter live in device memory, so the update is hipGraph-capturable
@@ -7,6 +7,11 @@ is honoured.  The same launch refreshes the bf16 compute copies of the weights i
 1x1-conv weights, whose compute layout is a plain cast), so those layers never re-derive them per step
 (:func:`.functional.maintain_compute_copies`).  CPU parameters use the same math in plain torch (the
 reference's CPU configuration).
+
+:class:`FusedLAMB` and :class:`FusedLARS` scale every tensor's update by a ratio of two L2 norms over the whole
+tensor, so their step is TWO launches (csrc/kernels/optim_trust.hip): the chunks' squared norms, then the update.
+Same device-resident hyper-parameters and step counter, same bf16 copy refresh, no host read and no allocation
+in ``step()``: capturable like the others.
 
 The per-parameter state uses torch's key names (``step``, ``exp_avg``, ``exp_avg_sq``,
 ``momentum_buffer``) so ``state_dict()`` round-trips with ``torch.optim`` and with the elastic
@@ -21,15 +26,17 @@ from . import functional as OF
 from . import streams
 
 _MODES = {"sgd": 0, "adam": 1, "adamw": 2}
+_TRUST = {"lamb": 0, "lars": 1}  # kinds of the two-launch trust-ratio step (multi_tensor_trust)
+_ADAM_STATE = ("adam", "adamw", "lamb")  # exp_avg + exp_avg_sq; the others: momentum_buffer with momentum != 0
 
 
 class _FusedBase(torch.optim.Optimizer):
     KIND = "adam"
 
     def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, momentum=0.0,
-                 grad_scale=1.0):
+                 grad_scale=1.0, **extra):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, momentum=momentum,
-                        grad_scale=grad_scale)
+                        grad_scale=grad_scale, **extra)
         super().__init__(params, defaults)
         self._dev = {}  # id(group) -> dict(table, sig, hp, hp_key, step)
 
@@ -47,17 +54,17 @@ class _FusedBase(torch.optim.Optimizer):
             s0 = self.state[params[0]].get("step") if params else None
             st["step"][0].fill_(int(s0) if s0 is not None else 0)
             self._dev[gi] = st
-        need_avg = self.KIND in ("adam", "adamw") or group["momentum"] != 0.0
+        need_avg = self.KIND in _ADAM_STATE or group["momentum"] != 0.0
         for p in params:
             state = self.state[p]
-            if self.KIND in ("adam", "adamw"):
+            if self.KIND in _ADAM_STATE:
                 if "exp_avg" not in state:
                     state["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
                     state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
             elif need_avg and "momentum_buffer" not in state:
                 state["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
         grads = [p.grad for p in params]
-        if self.KIND in ("adam", "adamw"):
+        if self.KIND in _ADAM_STATE:
             m = [self.state[p]["exp_avg"] for p in params]
             v = [self.state[p]["exp_avg_sq"] for p in params]
         else:
@@ -73,6 +80,9 @@ class _FusedBase(torch.optim.Optimizer):
             bf = [c.get("bf16", none) for c in copies]
             table, chunks, nchunks = C.optim_table([p.data for p in params], grads_c, m, v, bf)
             st.update(sig=sig, table=table, chunks=chunks, nchunks=nchunks, grads_keep=grads_c)
+            if self.KIND in _TRUST:  # per-tensor chunk spans + the float2[nchunks] norm workspace, made once
+                st["spans"], st["norms"], n = C.optim_trust_table([p.data for p in params])
+                assert n == nchunks
             # KxK conv weights: both bf16 GEMM layouts refreshed by one launch after the update
             kxk = [(p, c) for p, c in zip(params, copies) if "kxk" in c]
             st["conv_table"], st["nconv"], st["conv_blocks"] = None, 0, 0
@@ -84,13 +94,25 @@ class _FusedBase(torch.optim.Optimizer):
                 # x blocks per entry: the largest weight's 32x32 (co, ci) tiles (3x3 path) / 256-pair chunks
                 tiles = max(-(-c["kxk"][0] // 32) * -(-c["kxk"][1] // 32) for _, c in kxk)
                 st["conv_blocks"] = max(1, min(1024, tiles))
+        self._upload_hyper(st, group)
+        return st
+
+    def _upload_hyper(self, st, group):
         b1, b2 = group["betas"]
+        if self.KIND == "lars":
+            b1 = group["trust_coefficient"]  # HP_TRUST: the slot of beta1, which LARS has no use for
         hp_key = (group["lr"], b1, b2, group["eps"], group["weight_decay"], group["momentum"], group["grad_scale"])
         if st["hp_key"] != hp_key:
             # + HP_OMB1 / HP_OMB2: 1 - beta in double, then rounded (the kernel's 1.f - 0.999f is 1.3e-5 off)
             st["hp"].copy_(torch.tensor(list(hp_key) + [1.0 - b1, 1.0 - b2], dtype=torch.float32), non_blocking=False)
             st["hp_key"] = hp_key
-        return st
+
+    def sync_hyper_to_device(self):
+        """Upload hyper-parameters changed through ``param_groups`` to the device tables the update kernels read:
+        what a captured ``step()`` needs between hipGraph replays (an eager ``step()`` does it itself)."""
+        for gi, group in enumerate(self.param_groups):
+            if gi in self._dev:
+                self._upload_hyper(self._dev[gi], group)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -107,7 +129,11 @@ class _FusedBase(torch.optim.Optimizer):
                 C = C or _native.C()
                 streams.join(params[0].device)  # gradients written on the wgrad side stream
                 st = self._group_dev(gi, group, params)
-                C.optim_step(st["table"], st["chunks"], st["nchunks"], _MODES[self.KIND], st["hp"], st["step"])
+                if self.KIND in _TRUST:
+                    C.optim_trust_step(st["table"], st["chunks"], st["nchunks"], st["spans"], st["norms"],
+                                       _TRUST[self.KIND], st["hp"], st["step"])
+                else:
+                    C.optim_step(st["table"], st["chunks"], st["nchunks"], _MODES[self.KIND], st["hp"], st["step"])
                 if st["nconv"]:
                     C.conv_layouts_step(st["conv_table"], st["nconv"], st["conv_blocks"])
                 # host ``step`` is synchronised from the device counter by state_dict() (graph replays)
@@ -137,10 +163,11 @@ class _FusedBase(torch.optim.Optimizer):
 
     def supports_segments(self, params) -> bool:
         """True when :meth:`attach_update` / :meth:`step_range` can run this optimiser's update piecewise:
-        one GPU parameter group, no KxK conv layout copies to refresh."""
+        one GPU parameter group, no KxK conv layout copies to refresh, and not a trust-ratio kind (its update
+        needs the whole tensor's norms first)."""
         # (inspects the maintained copies without re-allocating them: maintain_compute_copies would replace the
         # copies the optimiser table writes)
-        return (len(self.param_groups) == 1 and all(p.is_cuda for p in params) and
+        return (self.KIND in _MODES and len(self.param_groups) == 1 and all(p.is_cuda for p in params) and
                 not any(getattr(p, "_pde_conv", False) and p.dim() == 4 and p.shape[2] * p.shape[3] > 1
                         for p in params) and
                 not any("kxk" in p.__dict__.get("_pde_maint", {}) for p in params))
@@ -170,6 +197,9 @@ class _FusedBase(torch.optim.Optimizer):
             state = self.state[p]
             state["step"] = state.get("step", 0) + 1
             t = state["step"]
+            if self.KIND in _TRUST:
+                self._cpu_trust(group, p, g, state, t)
+                continue
             if self.KIND == "sgd":
                 if wd != 0:
                     g = g.add(p, alpha=wd)
@@ -197,6 +227,37 @@ class _FusedBase(torch.optim.Optimizer):
             bc2 = 1 - b2 ** t
             denom = (v.sqrt() / (bc2 ** 0.5)).add_(eps)
             p.addcdiv_(m, denom, value=-lr / bc1)
+
+    def _cpu_trust(self, group, p, g, state, t):
+        """LAMB / LARS on one CPU tensor (``g`` already scaled by ``grad_scale``)."""
+        lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
+        pn = p.norm()
+        if self.KIND == "lamb":
+            if "exp_avg" not in state:
+                state["exp_avg"] = torch.zeros_like(p)
+                state["exp_avg_sq"] = torch.zeros_like(p)
+            m, v = state["exp_avg"], state["exp_avg_sq"]
+            m.lerp_(g, 1 - b1)
+            v.mul_(b2).addcmul_(g, g, value=1 - b2)
+            u = (m / (1 - b1 ** t)) / ((v / (1 - b2 ** t)).sqrt_().add_(eps))
+            if wd != 0:
+                u.add_(p, alpha=wd)
+            un = u.norm()
+            r = float(pn / un) if pn > 0 and un > 0 else 1.0
+            p.add_(u, alpha=-lr * r)
+            return
+        mom, gn = group["momentum"], g.norm()
+        r = float(group["trust_coefficient"] * pn / (gn + wd * pn + eps)) if pn > 0 and gn > 0 else 1.0
+        d = (g.add(p, alpha=wd) if wd != 0 else g) * r
+        if mom != 0:
+            buf = state.get("momentum_buffer")
+            if buf is None or t == 1:
+                buf = d.clone()
+            else:
+                buf.mul_(mom).add_(d)
+            state["momentum_buffer"] = buf
+            d = buf
+        p.add_(d, alpha=-lr)
 
     def sync_step_from_device(self):
         """Copy each GPU group's device step counter into the per-parameter host ``step``.  The device counter
@@ -239,3 +300,35 @@ class FusedAdamW(_FusedBase):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+
+
+class FusedLAMB(_FusedBase):
+    """LAMB (You et al. 2020): Adam's direction with a per-tensor trust ratio, two launches per step.
+
+        m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;  u = (m / bc1) / (sqrt(v / bc2) + eps) + wd p
+        r = |p| / |u| if both norms are positive, else 1;  p -= lr r u          (g' = grad_scale g)
+
+    Norms are L2 norms over each parameter tensor as handed over.  Not done here: excluding 1-D tensors (biases,
+    norm scales) from the adaptation, global gradient clipping, update segments attached to GEMM launches
+    (``supports_segments`` is False), and the in-kernel update of ``FusedCNN`` / ``MegaMLP``."""
+    KIND = "lamb"
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, grad_scale=1.0):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+
+
+class FusedLARS(_FusedBase):
+    """LARS (You et al. 2017): momentum SGD with a per-tensor trust ratio, two launches per step.
+
+        r = trust_coefficient |p| / (|g'| + wd |p| + eps) if |p| and |g'| are positive, else 1
+        d = r (g' + wd p);  m = d at step 1 or with momentum 0, else momentum m + d;  p -= lr m
+
+    ``momentum_buffer`` exists only with momentum != 0.  Not done here: excluding 1-D tensors from the adaptation,
+    Nesterov momentum, global gradient clipping, update segments attached to GEMM launches (``supports_segments``
+    is False), and the in-kernel update of ``FusedCNN`` / ``MegaMLP``."""
+    KIND = "lars"
+
+    def __init__(self, params, lr, momentum=0.9, weight_decay=0.0, trust_coefficient=1e-3, eps=1e-8,
+                 grad_scale=1.0):
+        super().__init__(params, lr=lr, momentum=momentum, weight_decay=weight_decay, eps=eps,
+                         grad_scale=grad_scale, trust_coefficient=trust_coefficient)
