@@ -994,6 +994,42 @@ void optim_trust_step(const Tensor& table, const Tensor& chunks, int64_t nchunks
         "optim_trust_step");
 }
 
+// Global-norm gradient clipping (optim_clip.hip) over the (table, chunks, nchunks, hp) of up to kClipMaxGroups param
+// groups, ONE launch: clip_ws (optim_clip_ws_floats(total chunks) fp32, zero at allocation, [CLIP_MAX_NORM] uploaded
+// by the caller) receives {total, coef} and every group's hp_eff.
+int64_t optim_clip_ws_floats(int64_t nchunks) { return pde::CLIP_PARTIALS + std::max<int64_t>(nchunks, 0); }
+// (max_norm, total, hp_eff, per-group stride) offsets of the workspace, in floats
+std::tuple<int64_t, int64_t, int64_t, int64_t> optim_clip_layout() {
+  return {pde::CLIP_MAX_NORM, pde::CLIP_TOTAL, pde::CLIP_HP_EFF, pde::HP_COUNT};
+}
+void optim_clip(const std::vector<Tensor>& tables, const std::vector<Tensor>& chunks,
+                const std::vector<int64_t>& nchunks, const std::vector<Tensor>& hparams, Tensor& clip_ws) {
+  const size_t n = tables.size();
+  TORCH_CHECK(n >= 1 && n <= static_cast<size_t>(pde::kClipMaxGroups), "optim_clip: 1..", pde::kClipMaxGroups,
+              " param groups, not ", n);
+  TORCH_CHECK(chunks.size() == n && nchunks.size() == n && hparams.size() == n, "optim_clip: list sizes");
+  CHECK_IN(clip_ws); CHECK_F32(clip_ws);
+  pde::ClipGroups g{};
+  int64_t total = 0;
+  for (size_t i = 0; i < n; ++i) {
+    CHECK_IN(tables[i]); CHECK_IN(chunks[i]); CHECK_IN(hparams[i]); CHECK_F32(hparams[i]);
+    TORCH_CHECK(hparams[i].numel() >= pde::HP_COUNT, "hparams size");
+    TORCH_CHECK(nchunks[i] > 0 && chunks[i].nbytes() == static_cast<size_t>(nchunks[i]) * sizeof(pde::OptimChunk) &&
+                    tables[i].nbytes() >= sizeof(pde::OptimEntry) && tables[i].device() == clip_ws.device(),
+                "optim_clip: group ", i, ": not the (table, chunks, nchunks) of one optim_table");
+    total += nchunks[i];
+    TORCH_CHECK(total < (1L << 31), "optim_clip: too many chunks");
+    g.tab[i] = reinterpret_cast<const pde::OptimEntry*>(tables[i].data_ptr());
+    g.chunks[i] = reinterpret_cast<const pde::OptimChunk*>(chunks[i].data_ptr());
+    g.hp[i] = hparams[i].data_ptr<float>();
+    g.c_end[i] = static_cast<int>(total);
+  }
+  g.ngroups = static_cast<int>(n);
+  TORCH_CHECK(clip_ws.numel() >= optim_clip_ws_floats(total), "optim_clip: the workspace holds ", clip_ws.numel(),
+              " floats, the launch needs ", optim_clip_ws_floats(total));
+  check(pde::multi_tensor_clip(g, clip_ws.data_ptr<float>(), cur_stream()), "optim_clip");
+}
+
 // Chunk range [c0, c1) of an optimiser table: its own launch (publish: the step's last segment advances the
 // device step counter), or -- optim_attach -- appended as extra blocks to the NEXT paired GEMM launch
 // (gemm_pair_end), so the HBM-bound update of one layer overlaps the latency-bound backward GEMMs of the next.
@@ -1568,13 +1604,21 @@ std::tuple<Tensor, Tensor, Tensor> mlp_eval(const Tensor& x, const optional<Tens
 // The update of `mode` over the flat CNN parameters + the fragment-image refresh, ONE launch, after a gradient
 // all-reduce that ran outside the reduction kernel (FusedCNN.opt_step).  step may be None for plain SGD.
 void cnn_opt(Tensor& params, const Tensor& grads, Tensor& frag, const Tensor& hp, const optional<Tensor>& step,
-             int64_t mode, const optional<Tensor>& m, const optional<Tensor>& v) {
+             int64_t mode, const optional<Tensor>& m, const optional<Tensor>& v, const optional<Tensor>& clip_ws) {
   CHECK_IN(params); CHECK_IN(grads); CHECK_F32(params); CHECK_F32(grads);
   TORCH_CHECK(params.numel() == pde::cnn_num_params() && grads.numel() == params.numel() &&
                   grads.device() == params.device(),
               "cnn_opt: params and grads must be the flat Net parameters and their gradient, on one device");
   check_cnn_frag(frag, "cnn_opt");
-  const pde::CnnUpdate u = cnn_update_from(params, mode, hp, step, m, v, "cnn_opt");
+  pde::CnnUpdate u = cnn_update_from(params, mode, hp, step, m, v, "cnn_opt");
+  if (clip_ws.has_value() && clip_ws->defined()) {  // the optimiser's clip workspace: the clipping variant
+    CHECK_IN(*clip_ws); CHECK_F32(*clip_ws);
+    TORCH_CHECK(clip_ws->numel() >= pde::CLIP_PARTIALS && clip_ws->device() == params.device(),
+                "cnn_opt: clip_ws must be an optimiser's clip workspace on the parameters' device");
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(grads.data_ptr()) & 15) == 0,
+                "cnn_opt: clipping reads the gradient with 16-byte loads");
+    u.clip = clip_ws->data_ptr<float>();
+  }
   check(pde::cnn_opt_fused(params.data_ptr<float>(), grads.data_ptr<float>(), frag.data_ptr(), u, cur_stream()),
         "cnn_opt");
 }
@@ -1617,7 +1661,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("xgmi_view") = py::none(), py::arg("xscale") = 1.0, py::arg("mode") = 0, py::arg("m") = py::none(),
         py::arg("v") = py::none());
   m.def("cnn_opt", &cnn_opt, py::arg("params"), py::arg("grads"), py::arg("frag"), py::arg("hp"), py::arg("step"),
-        py::arg("mode"), py::arg("m") = py::none(), py::arg("v") = py::none());
+        py::arg("mode"), py::arg("m") = py::none(), py::arg("v") = py::none(), py::arg("clip_ws") = py::none());
   m.def("cnn_adasum_step", &cnn_adasum_step, py::arg("params"), py::arg("grads"), py::arg("frag"), py::arg("hp"),
         py::arg("step"), py::arg("mode"), py::arg("m") = py::none(), py::arg("v") = py::none(), py::kw_only(),
         py::arg("xgmi_view"), py::arg("gram"), py::arg("gram_rows"));
@@ -1739,6 +1783,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("optim_step", &optim_step);
   m.def("optim_trust_table", &optim_trust_table);
   m.def("optim_trust_step", &optim_trust_step);
+  m.def("optim_clip", &optim_clip);
+  m.def("optim_clip_ws_floats", &optim_clip_ws_floats);
+  m.def("optim_clip_layout", &optim_clip_layout);
   m.def("optim_step_range", &optim_step_range);
   m.def("optim_chunk_elems", &pde::optim_chunk_elems);
   m.def("optim_attach", &optim_attach);

@@ -252,6 +252,32 @@ hipError_t multi_tensor_trust(int kind, const OptimEntry* dev_table, const Optim
                               const TrustSpan* dev_spans, float* dev_norms, const float* dev_hparams, int* dev_step,
                               hipStream_t s);
 
+// Global-norm gradient clipping (optim_clip.hip), torch.nn.utils.clip_grad_norm_ with grad_scale folded in:
+//   total = sqrt(sum over all groups of (grad_scale_g * g)^2),  coef = min(1, max_norm / (total + 1e-6)).
+// ONE launch over the tables of up to kClipMaxGroups param groups.  No update kernel changes: the launch writes, per
+// group, a second hyper-parameter table hp_eff = hp with HP_GRAD_SCALE multiplied by coef, and the unchanged update
+// kernels are then launched on hp_eff.  The clip workspace is one fp32 buffer of CLIP_PARTIALS + (chunks of all
+// groups) floats, zero at allocation; ws[CLIP_MAX_NORM] is uploaded by the host like hp.
+constexpr int kClipMaxGroups = 8;
+enum ClipWs {
+  CLIP_MAX_NORM = 0,  // in: max_norm
+  CLIP_TICKET = 1,    // the kernel's own arrival ticket (int bits; 0 between launches)
+  CLIP_TOTAL = 2,     // out: the norm before clipping
+  CLIP_COEF = 3,      // out: the clip coefficient
+  CLIP_HP_EFF = 4,    // out: float[kClipMaxGroups][HP_COUNT]
+  CLIP_PARTIALS = CLIP_HP_EFF + kClipMaxGroups * HP_COUNT,  // one float per chunk: its sum of raw g^2
+};
+struct ClipGroups {  // group i owns chunks [c_end[i-1], c_end[i]) of the launch, in its own chunk list's order
+  const OptimEntry* tab[kClipMaxGroups];
+  const OptimChunk* chunks[kClipMaxGroups];
+  const float* hp[kClipMaxGroups];
+  int c_end[kClipMaxGroups];
+  int ngroups;
+};
+// hipErrorInvalidValue on a group count outside 1..kClipMaxGroups, a null pointer, an empty group or c_end not
+// ascending.  hipGraph-capturable: no allocation, no host read.
+hipError_t multi_tensor_clip(const ClipGroups& g, float* clip_ws, hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------
 // BatchNorm / pooling / dropout / EmbeddingBag (norm_pool.hip).  Activations NHWC bf16, [P = N*H*W][C].
 // ---------------------------------------------------------------------------------------------
@@ -336,6 +362,9 @@ struct CnnUpdate {
   int* step;        // the optimiser's {steps taken, arrival ticket}, advanced on device; plain SGD: optional, [0] += 1
   float* m;         // modes 1..3: flat fp32 state indexed like params
   float* v;         // modes 2, 3
+  // cnn_opt_fused only: the optimiser's clip workspace (ClipWs; reads CLIP_MAX_NORM, writes CLIP_TOTAL / CLIP_COEF)
+  // -- the update runs on the gradient clipped to that global norm.  nullptr: no clipping.
+  float* clip = nullptr;
 };
 // The one home of the rules: the mode is 0..3; a stateful mode (1..3) needs hp, step and m; Adam and AdamW need v.
 // The launchers return hipErrorInvalidValue where it fails.
@@ -374,7 +403,8 @@ struct CnnTrainArgs {
 hipError_t cnn_train_fused(const CnnTrainArgs& a, hipStream_t s);
 // `u` on the all-reduced grads plus the fragment refresh, ONE launch: k_cnn_sgd for plain SGD (u.step may be
 // nullptr), k_cnn_opt<MODE> (optdev's numbering, converted in the launcher) for the stateful modes.  u.hp must be
-// set and frag 16-B aligned.
+// set and frag 16-B aligned.  With u.clip it is k_cnn_opt_clip<mode>, still ONE launch: every workgroup derives the
+// global gradient norm itself, in one fixed order, and updates on the clipped gradient (grads 16-B aligned then).
 hipError_t cnn_opt_fused(float* params, const float* grads, void* frag, const CnnUpdate& u, hipStream_t s);
 // hvd.Adasum of the ranks' weight DELTAS behind cnn_train_fused (no update, no exchange there: grads holds this
 // rank's local mean gradient), TWO launches on s, hipGraph-capturable:

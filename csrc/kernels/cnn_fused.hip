@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "adasum_weights.h"
+#include "clip_device.h"
 #include "common.cuh"
 #include "optim_device.h"
 #include "pde_kernels.h"
@@ -2047,10 +2048,98 @@ __global__ __launch_bounds__(256) void k_cnn_opt(float* __restrict__ params, con
   }
 }
 
+// k_cnn_sgd / k_cnn_opt with the gradient clipped to a global norm (torch.nn.utils.clip_grad_norm_, grad_scale folded
+// in; the formulas of optim_clip.hip), still ONE launch.  The whole gradient is NPARAM floats (85 KB, L2-resident
+// behind the all-reduce), so a grid-wide reduction is not worth a kernel boundary or a hand-off: EVERY workgroup of
+// k_cnn_opt's grid reads all of it -- CLIP_LD 16-byte loads per thread, all issued before any math, next to the
+// loads of its own parameter and state -- and reduces sum g^2 in one fixed order (a thread's elements in index
+// order, the wave's xor butterfly, the four waves in wave order), so every workgroup holds the bitwise same
+// coefficient.  The update is then the unclipped kernels' own (optdev::update / k_cnn_sgd's expression, write_frag,
+// the step ticket) with the grad scale multiplied by the coefficient; workgroup 0 stores {total, coef}.
+// MODE: the CnnUpdateMode (0 plain SGD .. 3 AdamW).
+constexpr int CLIP_LD = (NPARAM / 4 + 255) / 256;  // 22 float4 per thread
+static_assert(NPARAM % 4 == 0, "the flat gradient is read as float4");
+template <int MODE>
+__global__ __launch_bounds__(256) void k_cnn_opt_clip(float* __restrict__ params, const float* __restrict__ grads,
+                                                      float* __restrict__ m, float* __restrict__ v,
+                                                      const float* __restrict__ hp, int* __restrict__ step,
+                                                      uint16_t* __restrict__ frag, float* __restrict__ clip_ws) {
+  constexpr int OM = MODE == CNN_SGD ? 0 : MODE - CNN_SGD_STATE;  // optdev's numbering
+  __shared__ float s_part[4];
+  __shared__ int s_step;
+  f32x4 gl[CLIP_LD];
+#pragma unroll
+  for (int u = 0; u < CLIP_LD; ++u) {
+    const int j = u * 256 + static_cast<int>(threadIdx.x);
+    gl[u] = j < NPARAM / 4 ? *reinterpret_cast<const f32x4*>(grads + 4 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  const bool live = p < NPARAM;
+  float w = 0.f, g = 0.f, mm = 0.f, vv = 0.f;
+  if (live) {
+    w = params[p];
+    g = grads[p];
+    if constexpr (MODE != CNN_SGD) mm = m[p];
+    if constexpr (MODE >= CNN_ADAM) vv = v[p];
+  }
+  if constexpr (MODE != CNN_SGD) {
+    if (threadIdx.x == 0) s_step = step[0] + 1;  // (published by block_sum4's barrier)
+  }
+  float sq = 0.f;
+#pragma unroll
+  for (int u = 0; u < CLIP_LD; ++u) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sq = fmaf(gl[u][k], gl[u][k], sq);
+  }
+  const float gscale = hp[HP_GRAD_SCALE];
+  const float total = __fmul_rn(sqrtf(clipdev::block_sum4(wave_sum(sq), s_part)), fabsf(gscale));
+  const float coef = clipdev::clip_coef(total, clip_ws[CLIP_MAX_NORM]);
+  const float gs_eff = __fmul_rn(gscale, coef);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    clip_ws[CLIP_TOTAL] = total;
+    clip_ws[CLIP_COEF] = coef;
+  }
+  if constexpr (MODE == CNN_SGD) {
+    if (step != nullptr && blockIdx.x == 0 && threadIdx.x == 0) step[0] += 1;  // the optimiser's device step
+    if (live) {
+      w = w - hp[HP_LR] * (g * gs_eff);
+      params[p] = w;
+      write_frag(frag, p, w);
+    }
+  } else {
+    optdev::Hyper h = optdev::load_hyper<OM>(hp, s_step);
+    h.gscale = gs_eff;
+    if (live) {
+      optdev::update<OM>(h, w, g, mm, vv);
+      params[p] = w;
+      m[p] = mm;
+      if constexpr (MODE >= CNN_ADAM) v[p] = vv;
+      write_frag(frag, p, w);
+    }
+    __syncthreads();  // (every block read the old count before its arrival: the last one publishes)
+    if (threadIdx.x == 0) {
+      const int prev = atomicAdd(step + 1, 1);
+      if (prev == static_cast<int>(gridDim.x) - 1) {
+        step[0] = s_step;
+        step[1] = 0;
+      }
+    }
+  }
+}
+
 hipError_t cnn_opt_fused(float* params, const float* grads, void* frag, const CnnUpdate& u, hipStream_t s) {
   if (!cnn_update_valid(u) || u.hp == nullptr || (reinterpret_cast<uintptr_t>(frag) & 15))
     return hipErrorInvalidValue;
   uint16_t* fr = static_cast<uint16_t*>(frag);
+  if (u.clip != nullptr) {
+    if (reinterpret_cast<uintptr_t>(grads) & 15) return hipErrorInvalidValue;  // float4 gradient loads
+    using ClipFn = decltype(&k_cnn_opt_clip<0>);
+    static const ClipFn kClip[4] = {&k_cnn_opt_clip<CNN_SGD>, &k_cnn_opt_clip<CNN_SGD_STATE>,
+                                    &k_cnn_opt_clip<CNN_ADAM>, &k_cnn_opt_clip<CNN_ADAMW>};
+    hipLaunchKernelGGL(kClip[u.mode], dim3(ceil_div(NPARAM, 256)), dim3(256), 0, s, params, grads, u.m, u.v, u.hp,
+                       u.step, fr, u.clip);
+    return hipGetLastError();
+  }
   if (u.mode == CNN_SGD) {
     hipLaunchKernelGGL(k_cnn_sgd, dim3(ceil_div(NPARAM, 256)), dim3(256), 0, s, params, grads, u.hp, fr, u.step);
   } else {

@@ -52,7 +52,8 @@ from ..utils.config import add_runtime_args
 
 
 def load_train_objs(model_name: str, device, train_size: int, test_size: int, data_dir=None,
-                    momentum: float = 0.0, weight_decay: float = 0.0, optimizer: str | None = None):
+                    momentum: float = 0.0, weight_decay: float = 0.0, optimizer: str | None = None,
+                    clip_grad_norm: float | None = None):
     train_set, test_set = mnist_datasets(device, train_size, test_size, data_dir)
     allowed = ("sgd", "lars") if model_name == "cnn" else ("adam", "lamb")
     if optimizer is not None and optimizer not in allowed:
@@ -63,20 +64,23 @@ def load_train_objs(model_name: str, device, train_size: int, test_size: int, da
         model = Net()
         loss = OF.nll_loss
         # (mnist_horovod.py:50 is plain SGD; --momentum / --weight_decay: the fused step applies those too)
+        # --clip_grad_norm: global-norm gradient clipping in the optimiser (max_grad_norm), any of the four
+        clip = dict(max_grad_norm=clip_grad_norm)
         make_opt = lambda params: FusedSGD(params, lr=0.01, momentum=momentum,  # noqa: E731
-                                           weight_decay=weight_decay)
+                                           weight_decay=weight_decay, **clip)
         if optimizer == "lars":
             # the large-batch rule: the layer-wise ratio (trust coefficient 1e-3) carries a base rate near 1
             make_opt = lambda params: FusedLARS(params, lr=1.0, momentum=momentum or 0.9,  # noqa: E731
-                                                weight_decay=weight_decay)
+                                                weight_decay=weight_decay, **clip)
     else:
         from ..models.mlp import reference_mlp
 
         model = reference_mlp()
         loss = OF.cross_entropy
-        make_opt = lambda params: FusedAdam(params, lr=1e-3)  # noqa: E731  (mnist_ddp_elastic.py:173)
+        clip = dict(max_grad_norm=clip_grad_norm)
+        make_opt = lambda params: FusedAdam(params, lr=1e-3, **clip)  # noqa: E731  (mnist_ddp_elastic.py:173)
         if optimizer == "lamb":
-            make_opt = lambda params: FusedLAMB(params, lr=1e-3)  # noqa: E731
+            make_opt = lambda params: FusedLAMB(params, lr=1e-3, **clip)  # noqa: E731
     return train_set, test_set, model, make_opt, loss
 
 
@@ -135,9 +139,10 @@ class Trainer:
             world = self.ddp.world
             own_gpu = torch.cuda.device_count() >= int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
             single_node = int(os.environ.get("LOCAL_WORLD_SIZE", str(world))) == world
-            # (the one-launch step applies the update itself: only the kinds it knows, _MODES)
+            # (the one-launch step applies the update itself: only the kinds it knows, _MODES, and no global-norm
+            # clipping -- --clip_grad_norm takes the route --optimizer lamb takes: FusedMLP + optimizer.step())
             if (train_data.batch_size % 32 == 0 and os.environ.get("PDE_MLP_MEGA", "1") != "0" and
-                    getattr(self.optimizer, "KIND", "") in _MODES and
+                    getattr(self.optimizer, "KIND", "") in _MODES and self.optimizer.clip_max_norm() is None and
                     (world == 1 or (own_gpu and single_node and getattr(self.optimizer, "KIND", "") != "sgd"))):
                 from ..models.mlp_mega import MegaMLP
 
@@ -196,7 +201,7 @@ class Trainer:
             self.global_step += 1
 
     def _fused_cnn_step(self, source, targets):
-        from ..models.cnn_fused import fused_update_mode
+        from ..models.cnn_fused import clips_gradients, fused_update_mode
 
         xgmi = getattr(self.ddp.comm, "xgmi", None)
         if fused_update_mode(self.optimizer) is None:  # FusedLARS: its own two-launch step behind the all-reduce
@@ -204,7 +209,8 @@ class Trainer:
             self.ddp.sync_gradients()
             self.optimizer.step()
             return loss
-        if self.ddp.world == 1 or xgmi is not None:
+        if not clips_gradients(self.optimizer) and (self.ddp.world == 1 or xgmi is not None):
+            # (--clip_grad_norm: the norm needs the final gradient -- the clipping one-launch update below)
             # SGD (+ momentum / weight decay) + fragment refresh inside the slab reduction, which at world > 1 also
             # exchanges the gradients over xGMI (an xgmi of size 1 is ignored)
             return self.fused.forward_backward(source, targets, grad_out=self.ddp.flat_grad, sgd=self.optimizer,
@@ -325,6 +331,9 @@ def build_parser():
     parser.add_argument("--optimizer", default=None, choices=["adam", "lamb", "sgd", "lars"],
                         help="mlp: adam (default) or lamb; cnn: sgd (default) or lars -- the trust-ratio optimisers "
                              "of ops/optim.py (two launches per step)")
+    parser.add_argument("--clip_grad_norm", type=float, default=None, metavar="X",
+                        help="clip the gradient to global L2 norm X before the update (torch clip_grad_norm_ "
+                             "semantics, on the GPU inside the optimiser step; default: none)")
     parser.add_argument("--fused", action="store_true",
                         help="cnn: whole-network fused training kernel (GPU; the default GPU path, kept for scripts)")
     parser.add_argument("--layers", action="store_true",
@@ -371,7 +380,7 @@ def main(argv=None):
         train_set, test_set, model, make_opt, criterion = load_train_objs(args.model, ctx.device, args.train_size,
                                                                           args.test_size, args.data_dir,
                                                                           args.momentum, args.weight_decay,
-                                                                          args.optimizer)
+                                                                          args.optimizer, args.clip_grad_norm)
         train_data = ShardedLoader(train_set, args.batch_size, ctx.world_size, ctx.rank, shuffle=True)
         test_data = ShardedLoader(test_set, args.batch_size, ctx.world_size, ctx.rank, shuffle=False)
         trainer = Trainer(ctx, model, train_data, test_data, make_opt, criterion, args.save_every,

@@ -45,6 +45,9 @@ def build_parser():
     ap.add_argument("--weight-decay", type=float, default=0.0, help="SGD L2 weight decay (default: 0)")
     ap.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
                     help="lars: ops/optim.py FusedLARS, momentum 0.9 unless --momentum is given (two launches per step)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                    help="clip the all-reduced gradient to global L2 norm X before the update (torch "
+                         "clip_grad_norm_ semantics, inside the optimiser step; default: none)")
     ap.add_argument("--train-size", type=int, default=60000)
     ap.add_argument("--data-dir", default=None,
                     help="directory with the four MNIST IDX files (plain or .gz; also DIR/MNIST/raw, DIR/raw); never "
@@ -80,9 +83,10 @@ def main(argv=None):
         args.lr = 1.0 if args.optimizer == "lars" else 0.01
     if args.optimizer == "lars":
         optimizer = FusedLARS(model.parameters(), lr=args.lr, momentum=args.momentum or 0.9,
-                              weight_decay=args.weight_decay)
+                              weight_decay=args.weight_decay, max_grad_norm=args.clip_grad_norm)
     else:
-        optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
+        optimizer = FusedSGD(model.parameters(), lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
+                             max_grad_norm=args.clip_grad_norm)
     if args.use_adasum:  # (FusedHvdStep: the fused kernel's local gradients + the two Adasum launches on the deltas)
         optimizer = hvd.DistributedOptimizer(optimizer, named_parameters=model.named_parameters(),
                                              compression=getattr(hvd.Compression, args.compression), op=hvd.Adasum)

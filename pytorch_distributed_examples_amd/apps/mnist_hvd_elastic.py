@@ -37,7 +37,7 @@ from ..utils import config as rtconfig
 from ..utils.config import add_runtime_args
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="Horovod-elastic MNIST CNN")
     ap.add_argument("--epochs", type=int, default=15)
     ap.add_argument("--batches-per-commit", type=int, default=30)
@@ -51,8 +51,15 @@ def main(argv=None):
     ap.add_argument("--device", default="auto", choices=["auto", "cpu", "gpu"])
     ap.add_argument("--layers", action="store_true", help="GPU: the autograd layer path instead of the fused step")
     ap.add_argument("--no-graph", action="store_true", help="GPU fused step without hipGraph capture")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                    help="clip the all-reduced gradient to global L2 norm X before AdamW (torch clip_grad_norm_ "
+                         "semantics, inside the optimiser step; default: none)")
     add_runtime_args(ap)
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     _cfg = rtconfig.apply(rtconfig.from_args(args))
     if hasattr(args, "device"):
         args.device = rtconfig.device_for(_cfg, args.device)
@@ -63,7 +70,7 @@ def main(argv=None):
     train_set, test_set = mnist_datasets(dev, args.train_size, args.test_size, args.data_dir)
 
     model = Net().to(dev)
-    optimizer = FusedAdamW(model.parameters(), lr=lr / math.sqrt(hvd.size()))
+    optimizer = FusedAdamW(model.parameters(), lr=lr / math.sqrt(hvd.size()), max_grad_norm=args.clip_grad_norm)
     optimizer = hvd.DistributedOptimizer(optimizer, named_parameters=model.named_parameters())
     step_counter = {"n": 0}
     fused_step = None

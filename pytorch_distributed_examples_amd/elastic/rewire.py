@@ -473,7 +473,9 @@ def run_elastic(args):
     else:
         dev = torch.device("cpu")
     train_set, test_set, model, make_opt, criterion = load_train_objs(args.model, dev, args.train_size,
-                                                                      args.test_size, getattr(args, "data_dir", None))
+                                                                      args.test_size, getattr(args, "data_dir", None),
+                                                                      clip_grad_norm=getattr(args, "clip_grad_norm",
+                                                                                             None))
     model = model.to(dev)
     optimizer = make_opt(model.parameters())
     pos = {"epoch": 0, "seen": 0}  # samples of the current epoch consumed by the whole group
@@ -711,6 +713,9 @@ def run_elastic_fused(args, report=None):
     from ..utils.graph import CapturedSteps
     from ..utils.log import RankLogger
 
+    if getattr(args, "clip_grad_norm", None) is not None:
+        raise SystemExit("--rewire --fused keeps plain SGD inside the slab reduction: --clip_grad_norm is not wired "
+                         "into it")
     if "PDE_ELASTIC_STORE" not in os.environ:
         raise SystemExit("--rewire needs the elastic driver (launch.hvdrun)")
     rdzv = RendezvousClient()

@@ -24,6 +24,9 @@ AdamW, :41-42), captured into a hipGraph.
   Without an xGMI plane, with an optimiser :func:`fused_update_mode` rejects, or with ``PDE_CNN_ADASUM_FUSED=0`` (the
   A/B switch), every step is ``forward_backward`` + ``opt.step()``: the same numbers through the optimiser's
   ``_foreach`` copies and the stand-alone exchange.
+* ``max_grad_norm`` on the wrapped optimiser (global-norm gradient clipping): the route is ``opt_step`` at every
+  world size -- the clipping one-launch update behind the all-reduce, three launches -- and an Adasum wrapper keeps
+  ``forward_backward`` + ``opt.step()``.
 """
 from __future__ import annotations
 
@@ -31,14 +34,18 @@ import os
 
 import torch
 
-from ..models.cnn_fused import FusedCNN, fused_update_mode
+from ..models.cnn_fused import FusedCNN, clips_gradients, fused_update_mode
 
 
 def adasum_update_mode(opt) -> int | None:
     """The fused update mode (:func:`..models.cnn_fused.fused_update_mode`) of an ``hvd.DistributedOptimizer(...,
     op=hvd.Adasum)`` whose local step the Adasum launches of the fused CNN can take; ``None`` for an optimiser that
-    is not an Adasum wrapper or wraps anything else.  Pure: needs no native module."""
-    return fused_update_mode(opt) if getattr(opt, "_adasum", False) else None
+    is not an Adasum wrapper or wraps anything else -- or clips to a global gradient norm (``max_grad_norm``): the
+    delta launch takes the local update unclipped, so such an optimiser keeps ``forward_backward`` + ``opt.step()``,
+    which clips by itself.  Pure: needs no native module."""
+    if not getattr(opt, "_adasum", False) or clips_gradients(opt):
+        return None
+    return fused_update_mode(opt)
 
 
 def adasum_fused_enabled() -> bool:
@@ -65,6 +72,11 @@ class FusedHvdStep:
         self.adasum_steps = 0  # steps taken by the two Adasum launches
         sgd = self.mode in (0, 1) and not self.adasum
         self.in_reduce = self.mode in (0, 1) or (self.mode is not None and opt_in_reduce_enabled())
+        # max_grad_norm: the update inside the reduction would run before the gradient is final -- the clipping
+        # one-launch update (FusedCNN.opt_step) at every world size, world 1 included
+        self.clip = clips_gradients(optimizer)
+        if self.clip:
+            self.in_reduce = False
         self.fused.always_prep = self.mode is None
         if not sgd:
             from ..ops import functional as OF

@@ -150,7 +150,16 @@ class FusedCNN:
         a gradient all-reduce that ran outside the reduction kernel.  The update math and the device step counter are
         the optimiser's own (optim_device.h)."""
         mode, st, params, m, v = self._update_args(opt)
-        _native.C().cnn_opt(self.flat, grads, self.frag, st["hp"], st["step"], mode=mode, m=m, v=v)
+        hp, clip_ws = st["hp"], None
+        if clips_gradients(opt) and cnn_clip_fused_enabled():
+            # max_grad_norm: k_cnn_opt_clip<mode>, still one launch -- every workgroup derives the global norm of
+            # the (all-reduced) gradient itself; {total, coef} land in opt.last_grad_norm
+            clip_ws = opt._clip_dev(self.flat.device, st["nchunks"])["ws"]
+        elif clips_gradients(opt):
+            # the two-launch composition: the optimiser's k_grad_clip over p.grad (the caller's flat gradient's
+            # views), then the unclipped update kernel on the hyper-parameter table that carries the coefficient
+            hp = opt._clip_step([(0, opt.param_groups[0], params)])[0][0]
+        _native.C().cnn_opt(self.flat, grads, self.frag, hp, st["step"], mode=mode, m=m, v=v, clip_ws=clip_ws)
         self._after_update(opt, params)
 
     @torch.no_grad()
@@ -220,6 +229,10 @@ class FusedCNN:
         if sgd is not None and opt is not None:
             raise ValueError("forward_backward: pass the optimiser as sgd= or opt=, not both")
         opt = sgd if opt is None else opt
+        if opt is not None and clips_gradients(opt):
+            raise ValueError("forward_backward: the update inside the slab reduction runs before the gradient is "
+                             "final, so it cannot clip to a global norm (max_grad_norm): call forward_backward "
+                             "without the optimiser, then opt_step")
         if grad_out is None:
             grad_out = self.grad_buffer()
         x = x.float().contiguous()
@@ -286,6 +299,19 @@ def fused_update_mode(opt) -> int | None:
         group = opt.param_groups[0]
         return 0 if group["momentum"] == 0.0 and group["weight_decay"] == 0.0 else 1
     return 2 if isinstance(opt, FusedAdam) else 3
+
+
+def clips_gradients(opt) -> bool:
+    """``opt`` (a fused optimiser, or a ``hvd.DistributedOptimizer`` around one) clips to a global gradient norm
+    (``max_grad_norm``): its update cannot ride in the slab reduction, :meth:`FusedCNN.opt_step` takes the clipping
+    variant.  Pure: needs no native module."""
+    return any(g.get("max_grad_norm") is not None for g in getattr(opt, "param_groups", ()))
+
+
+def cnn_clip_fused_enabled() -> bool:
+    """:meth:`FusedCNN.opt_step` of a clipping optimiser as ONE launch (``k_cnn_opt_clip``); ``PDE_CNN_CLIP_FUSED=0``
+    is the A/B switch to the two-launch composition ``k_grad_clip`` + the unclipped update on ``hp_eff``."""
+    return os.environ.get("PDE_CNN_CLIP_FUSED", "1") != "0"
 
 
 def opt_in_reduce_enabled() -> bool:

@@ -61,7 +61,10 @@ class MegaMLP:
         for i, L in enumerate(self.layers):
             assert L.bias is not None and L.relu == (i < len(self.layers) - 1), "Linear+ReLU stack, plain last layer"
         assert len(opt.param_groups) == 1, "one optimiser parameter group"
-        self.params = [p for L in self.layers for p in (L.weight, L.bias)]
+        if opt.param_groups[0].get("max_grad_norm") is not None:
+            raise ValueError("MegaMLP: the in-launch update runs layer by layer, before a global gradient norm "
+                             "exists -- max_grad_norm needs the layer-wise step + opt.step()")
+        self.params =[p for L in self.layers for p in (L.weight, L.bias)]
         assert [id(p) for p in opt.param_groups[0]["params"]] == [id(p) for p in self.params], \
             "the optimiser must hold exactly the model's parameters, in model order"
         self.mode = _MODES[opt.KIND]

@@ -16,6 +16,14 @@ in ``step()``: capturable like the others.
 The per-parameter state uses torch's key names (``step``, ``exp_avg``, ``exp_avg_sq``,
 ``momentum_buffer``) so ``state_dict()`` round-trips with ``torch.optim`` and with the elastic
 ``TorchState`` commit/restore.
+
+``max_grad_norm=X`` on any of the five classes clips the gradient to a global L2 norm first, with
+``torch.nn.utils.clip_grad_norm_``'s semantics and ``grad_scale`` folded in: ``g' = grad_scale g``, ``total =
+sqrt(sum g'^2)`` over every parameter of every group that has a gradient, ``coef = min(1, X / (total + 1e-6))``, and
+the update runs on ``coef g'``.  On the GPU that is ONE more launch per step (csrc/kernels/optim_clip.hip): it
+reduces the norm and writes, per group, a second hyper-parameter table whose ``grad_scale`` carries ``coef``; the
+unchanged update kernels then run on that table.  ``last_grad_norm`` is the device tensor ``{total, coef}``; no host
+read, so the step stays capturable, and ``max_grad_norm`` lives in device memory like the other hyper-parameters.
 """
 from __future__ import annotations
 
@@ -34,11 +42,54 @@ class _FusedBase(torch.optim.Optimizer):
     KIND = "adam"
 
     def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, momentum=0.0,
-                 grad_scale=1.0, **extra):
+                 grad_scale=1.0, max_grad_norm=None, **extra):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, momentum=momentum,
-                        grad_scale=grad_scale, **extra)
+                        grad_scale=grad_scale, max_grad_norm=max_grad_norm, **extra)
         super().__init__(params, defaults)
         self._dev = {}  # id(group) -> dict(table, sig, hp, hp_key, step)
+        self._clip = None  # dict(ws, key, nchunks): the clip workspace (pde_kernels.h ClipWs), made on first use
+
+    # -- global-norm clipping --------------------------------------------------------------------
+    def clip_max_norm(self):
+        """The optimiser's ``max_grad_norm``, or ``None`` when it does not clip.  One norm spans all groups, so the
+        groups must agree (``.get``: a param group saved before the option existed has no such key)."""
+        vals = {g.get("max_grad_norm") for g in self.param_groups}
+        if len(vals) > 1:
+            raise ValueError(f"max_grad_norm must be the same in every param group (one global norm), not {vals}")
+        return next(iter(vals)) if vals else None
+
+    def _clip_dev(self, device, nchunks: int):
+        """The clip workspace, sized for ``nchunks`` chunks, with ``max_grad_norm`` uploaded when it changed."""
+        C = _native.C()
+        cl = self._clip
+        if cl is None or "ws" not in cl or cl["nchunks"] < nchunks or cl["ws"].device != device:
+            ws = torch.zeros(C.optim_clip_ws_floats(nchunks), dtype=torch.float32, device=device)
+            cl = self._clip = {"ws": ws, "nchunks": nchunks, "key": None, "layout": C.optim_clip_layout()}
+        self._upload_clip(cl)
+        return cl
+
+    def _upload_clip(self, cl):
+        key = float(self.clip_max_norm())
+        if cl["key"] != key:
+            o = cl["layout"][0]
+            cl["ws"][o:o + 1].copy_(torch.tensor([key], dtype=torch.float32), non_blocking=False)
+            cl["key"] = key
+
+    def _hp_eff(self, cl, slot: int):
+        _, _, o, n = cl["layout"]
+        return cl["ws"][o + slot * n:o + (slot + 1) * n]
+
+    @property
+    def last_grad_norm(self):
+        """Device tensor ``{total, coef}`` of the last clipped GPU step -- the norm before clipping, as
+        ``clip_grad_norm_`` returns it, and the coefficient applied -- without a synchronisation; ``None`` before
+        the first one.  (CPU parameters: a host tensor of the same two numbers.)"""
+        if self._clip is None:
+            return None
+        if "host" in self._clip:
+            return self._clip["host"]
+        o = self._clip["layout"][1]
+        return self._clip["ws"][o:o + 2]
 
     # -- GPU -----------------------------------------------------------------------------------
     def _group_dev(self, gi, group, params):
@@ -113,6 +164,8 @@ class _FusedBase(torch.optim.Optimizer):
         for gi, group in enumerate(self.param_groups):
             if gi in self._dev:
                 self._upload_hyper(self._dev[gi], group)
+        if self._clip is not None and "ws" in self._clip and self.clip_max_norm() is not None:
+            self._upload_clip(self._clip)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -121,32 +174,63 @@ class _FusedBase(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         C = None
-        for gi, group in enumerate(self.param_groups):
-            params = [p for p in group["params"] if p.grad is not None]
-            if not params:
-                continue
+        live = [(gi, group, [p for p in group["params"] if p.grad is not None])
+                for gi, group in enumerate(self.param_groups)]
+        live = [t for t in live if t[2]]
+        hp_eff, cpu_coef = self._clip_step(live) if live and self.clip_max_norm() is not None else ({}, None)
+        for gi, group, params in live:
             if params[0].is_cuda:
                 C = C or _native.C()
                 streams.join(params[0].device)  # gradients written on the wgrad side stream
                 st = self._group_dev(gi, group, params)
+                hp = hp_eff.get(gi, st["hp"])  # clipping: the group's table with coef in its grad scale
                 if self.KIND in _TRUST:
                     C.optim_trust_step(st["table"], st["chunks"], st["nchunks"], st["spans"], st["norms"],
-                                       _TRUST[self.KIND], st["hp"], st["step"])
+                                       _TRUST[self.KIND], hp, st["step"])
                 else:
-                    C.optim_step(st["table"], st["chunks"], st["nchunks"], _MODES[self.KIND], st["hp"], st["step"])
+                    C.optim_step(st["table"], st["chunks"], st["nchunks"], _MODES[self.KIND], hp, st["step"])
                 if st["nconv"]:
                     C.conv_layouts_step(st["conv_table"], st["nconv"], st["conv_blocks"])
                 # host ``step`` is synchronised from the device counter by state_dict() (graph replays)
             else:
-                self._cpu_step(group, params)
+                self._cpu_step(group, params, cpu_coef)
         OF.bump_weight_generation()
         return loss
+
+    def _clip_step(self, live):
+        """The clipping half of ``step()`` over ``live`` = [(group index, group, params with a gradient)].  GPU: ONE
+        ``optim_clip`` launch over all groups' tables; returns ({group index: hp_eff}, None).  CPU: the coefficient
+        in torch, ``clip_grad_norm_``'s own operations; returns ({}, coef)."""
+        max_norm = self.clip_max_norm()
+        if not live[0][2][0].is_cuda:
+            norms = []
+            for _, group, params in live:
+                gs = group["grad_scale"]
+                norms += [torch.linalg.vector_norm(p.grad if gs == 1.0 else p.grad * gs) for p in params]
+            total = torch.linalg.vector_norm(torch.stack(norms))
+            coef = torch.clamp(max_norm / (total + 1e-6), max=1.0)
+            self._clip = {"host": torch.stack([total, coef])}
+            return {}, coef
+        C = _native.C()
+        if len(live) > 8:
+            raise ValueError(f"max_grad_norm: at most 8 param groups with a gradient, not {len(live)}")
+        dev = live[0][2][0].device
+        if any(not p.is_cuda or p.device != dev for _, _, ps in live for p in ps):
+            raise ValueError("max_grad_norm: one norm spans all parameters, which must be on one device")
+        streams.join(dev)
+        sts = [self._group_dev(gi, group, params) for gi, group, params in live]
+        cl = self._clip_dev(dev, sum(st["nchunks"] for st in sts))
+        C.optim_clip([st["table"] for st in sts], [st["chunks"] for st in sts], [st["nchunks"] for st in sts],
+                     [st["hp"] for st in sts], cl["ws"])
+        return {gi: self._hp_eff(cl, slot) for slot, (gi, _, _) in enumerate(live)}, None
 
     # -- update segments: one layer's update appended to a later backward GEMM launch ------------
     def _segment(self, subset):
         """(table, chunks, c0, c1, mode, hp, step) of ``subset`` -- parameters contiguous in the (single, GPU)
         param group's order -- for ``optim_attach`` / ``optim_step_range``."""
         assert len(self.param_groups) == 1, "update segments: one parameter group"
+        if self.clip_max_norm() is not None:
+            raise ValueError("update segments run before the global gradient norm exists: not with max_grad_norm")
         group = self.param_groups[0]
         params = [p for p in group["params"] if p.grad is not None]
         st = self._group_dev(0, group, params)
@@ -163,11 +247,13 @@ class _FusedBase(torch.optim.Optimizer):
 
     def supports_segments(self, params) -> bool:
         """True when :meth:`attach_update` / :meth:`step_range` can run this optimiser's update piecewise:
-        one GPU parameter group, no KxK conv layout copies to refresh, and not a trust-ratio kind (its update
-        needs the whole tensor's norms first)."""
+        one GPU parameter group, no KxK conv layout copies to refresh, not a trust-ratio kind (its update
+        needs the whole tensor's norms first) and no ``max_grad_norm`` (a segment would run before the global norm
+        exists)."""
         # (inspects the maintained copies without re-allocating them: maintain_compute_copies would replace the
         # copies the optimiser table writes)
-        return (self.KIND in _MODES and len(self.param_groups) == 1 and all(p.is_cuda for p in params) and
+        return (self.KIND in _MODES and len(self.param_groups) == 1 and self.clip_max_norm() is None and
+                all(p.is_cuda for p in params) and
                 not any(getattr(p, "_pde_conv", False) and p.dim() == 4 and p.shape[2] * p.shape[3] > 1
                         for p in params) and
                 not any("kxk" in p.__dict__.get("_pde_maint", {}) for p in params))
@@ -189,11 +275,13 @@ class _FusedBase(torch.optim.Optimizer):
             OF.bump_weight_generation()
 
     # -- CPU reference math (torch.optim semantics) ---------------------------------------------
-    def _cpu_step(self, group, params):
+    def _cpu_step(self, group, params, coef=None):
         lr, (b1, b2), eps = group["lr"], group["betas"], group["eps"]
         wd, mom, gs = group["weight_decay"], group["momentum"], group["grad_scale"]
         for p in params:
             g = p.grad if gs == 1.0 else p.grad * gs
+            if coef is not None:  # max_grad_norm: the clip coefficient of _clip_step (a 0-dim tensor)
+                g = g * coef
             state = self.state[p]
             state["step"] = state.get("step", 0) + 1
             t = state["step"]
@@ -279,27 +367,33 @@ class _FusedBase(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._dev = {}
+        self._clip = None
 
 
 class FusedSGD(_FusedBase):
     KIND = "sgd"
 
-    def __init__(self, params, lr, momentum=0.0, weight_decay=0.0, grad_scale=1.0):
-        super().__init__(params, lr=lr, momentum=momentum, weight_decay=weight_decay, grad_scale=grad_scale)
+    def __init__(self, params, lr, momentum=0.0, weight_decay=0.0, grad_scale=1.0, max_grad_norm=None):
+        super().__init__(params, lr=lr, momentum=momentum, weight_decay=weight_decay, grad_scale=grad_scale,
+                         max_grad_norm=max_grad_norm)
 
 
 class FusedAdam(_FusedBase):
     KIND = "adam"
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0,
+                 max_grad_norm=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
+                         max_grad_norm=max_grad_norm)
 
 
 class FusedAdamW(_FusedBase):
     KIND = "adamw"
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0):
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0,
+                 max_grad_norm=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
+                         max_grad_norm=max_grad_norm)
 
 
 class FusedLAMB(_FusedBase):
@@ -308,13 +402,16 @@ class FusedLAMB(_FusedBase):
         m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;  u = (m / bc1) / (sqrt(v / bc2) + eps) + wd p
         r = |p| / |u| if both norms are positive, else 1;  p -= lr r u          (g' = grad_scale g)
 
-    Norms are L2 norms over each parameter tensor as handed over.  Not done here: excluding 1-D tensors (biases,
-    norm scales) from the adaptation, global gradient clipping, update segments attached to GEMM launches
+    Norms are L2 norms over each parameter tensor as handed over.  ``max_grad_norm`` clips the gradient to a
+    global norm before everything else (apex ``FusedLAMB(max_grad_norm=...)``), one more launch.  Not done here:
+    excluding 1-D tensors (biases, norm scales) from the adaptation, update segments attached to GEMM launches
     (``supports_segments`` is False), and the in-kernel update of ``FusedCNN`` / ``MegaMLP``."""
     KIND = "lamb"
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, grad_scale=1.0):
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale)
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, grad_scale=1.0,
+                 max_grad_norm=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
+                         max_grad_norm=max_grad_norm)
 
 
 class FusedLARS(_FusedBase):
@@ -323,12 +420,13 @@ class FusedLARS(_FusedBase):
         r = trust_coefficient |p| / (|g'| + wd |p| + eps) if |p| and |g'| are positive, else 1
         d = r (g' + wd p);  m = d at step 1 or with momentum 0, else momentum m + d;  p -= lr m
 
-    ``momentum_buffer`` exists only with momentum != 0.  Not done here: excluding 1-D tensors from the adaptation,
-    Nesterov momentum, global gradient clipping, update segments attached to GEMM launches (``supports_segments``
-    is False), and the in-kernel update of ``FusedCNN`` / ``MegaMLP``."""
+    ``momentum_buffer`` exists only with momentum != 0.  ``max_grad_norm``: global-norm gradient clipping first,
+    one more launch.  Not done here: excluding 1-D tensors from the adaptation, Nesterov momentum, update segments
+    attached to GEMM launches (``supports_segments`` is False), and the in-kernel update of ``FusedCNN`` /
+    ``MegaMLP``."""
     KIND = "lars"
 
     def __init__(self, params, lr, momentum=0.9, weight_decay=0.0, trust_coefficient=1e-3, eps=1e-8,
-                 grad_scale=1.0):
+                 grad_scale=1.0, max_grad_norm=None):
         super().__init__(params, lr=lr, momentum=momentum, weight_decay=weight_decay, eps=eps,
-                         grad_scale=grad_scale, trust_coefficient=trust_coefficient)
+                         grad_scale=grad_scale, max_grad_norm=max_grad_norm, trust_coefficient=trust_coefficient)
