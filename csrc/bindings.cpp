@@ -15,6 +15,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "gemm_fp8.h"
 #include "mlp_eval.h"
 #include "mlp_train.h"
 #include "pde_kernels.h"
@@ -1651,6 +1652,146 @@ void cnn_adasum_step(Tensor& params, const Tensor& grads, Tensor& frag, const Te
         "cnn_adasum_step");
 }
 
+// ------------------------------------------------------------------------------------------------
+// FP8 linear layers (csrc/kernels/gemm_fp8.hip)
+// ------------------------------------------------------------------------------------------------
+pde::Fp8Rec* fp8_recs(const Tensor& recs, int64_t need, const char* what) {
+  CHECK_IN(recs); CHECK_F32(recs);
+  TORCH_CHECK(recs.dim() == 2 && recs.size(1) == 4 && need < recs.size(0), what, ": scale records must be fp32 [T][4]");
+  return reinterpret_cast<pde::Fp8Rec*>(recs.data_ptr<float>());
+}
+
+// An FP8 byte matrix [>= rows][ld]: contiguous uint8, 16-byte aligned, ld a multiple of `mult` and >= cols.
+const Tensor& fp8_mat(const Tensor& t, int64_t rows, int64_t cols, int mult, const char* what) {
+  CHECK_IN(t);
+  TORCH_CHECK(t.scalar_type() == at::kByte && t.dim() == 2, what, " must be a 2-D uint8 tensor of FP8 bytes");
+  TORCH_CHECK(t.size(0) >= rows && t.size(1) >= cols && t.size(1) % mult == 0 && t.size(1) < (1L << 30) &&
+                  al16(t.data_ptr()), what, " must be [>= ",
+              rows, "][>= ", cols, ", a multiple of ", mult, "], 16-byte aligned; got [", t.size(0), "][", t.size(1), "]");
+  return t;
+}
+
+// One quantiser entry: src ([rows][cols] fp32 or bf16 row view) -> dst and, where dst_t is not an empty tensor, the
+// transposed dst_t; rec: the tensor's row of the scale records `recs`.
+pde::Fp8QuantEntry fp8_entry(const Tensor& s, const Tensor& dst, const Tensor& dst_t, int64_t rec, const Tensor& recs,
+                             const char* what) {
+  CHECK_DEV(s); CHECK_F32_OR_BF16(s);
+  TORCH_CHECK(s.dim() == 2 && s.stride(1) == 1 && s.numel() > 0, what, ": a source is a 2-D row view");
+  constexpr int64_t kMax = 1L << 30;  // rows, cols and pitches are ints in the kernel
+  TORCH_CHECK(s.size(0) < kMax && s.size(1) < kMax && s.stride(0) >= s.size(1) && s.stride(0) < kMax, what,
+              ": source of ", s.size(0), " x ", s.size(1), " rows of pitch ", s.stride(0), " is out of range");
+  fp8_recs(recs, 0, what);
+  TORCH_CHECK(rec >= 0 && rec < recs.size(0), what, ": scale record ", rec, " of ", recs.size(0));
+  pde::Fp8QuantEntry e{};
+  e.src = s.data_ptr();
+  e.rows = s.size(0); e.cols = s.size(1); e.lds = s.stride(0);
+  e.bf16 = s.scalar_type() == at::kBFloat16;
+  e.dst = fp8_mat(dst, e.rows, e.cols, 64, what).data_ptr<uint8_t>();
+  e.ldd = dst.size(1);
+  if (dst_t.defined() && dst_t.numel() > 0) {
+    e.dstT = fp8_mat(dst_t, e.cols, e.rows, 64, what).data_ptr<uint8_t>();
+    e.ldt = dst_t.size(1);
+  }
+  e.rec = static_cast<int>(rec);
+  return e;
+}
+
+// Device table of one fp8_quant launch over srcs[i] -> dsts[i] (, dsts_t[i]) with records rec[i] of `recs` (the
+// tensor later passed to fp8_quant).  Returns (table, blocks_x).
+std::tuple<Tensor, int64_t> fp8_quant_table(const std::vector<Tensor>& srcs, const std::vector<Tensor>& dsts,
+                                            const std::vector<Tensor>& dsts_t, const std::vector<int64_t>& rec,
+                                            const Tensor& recs) {
+  const size_t n = srcs.size();
+  TORCH_CHECK(n > 0 && n < 65536 && dsts.size() == n && dsts_t.size() == n && rec.size() == n,
+              "fp8_quant_table: list sizes");
+  std::vector<pde::Fp8QuantEntry> tab(n);
+  long tiles = 1;
+  for (size_t i = 0; i < n; ++i) {
+    tab[i] = fp8_entry(srcs[i], dsts[i], dsts_t[i], rec[i], recs, "fp8_quant_table");
+    tiles = std::max<long>(tiles, static_cast<long>((tab[i].rows + 63) / 64) * (tab[i].ldd / 64));
+  }
+  Tensor table = to_device_bytes(tab.data(), static_cast<long>(n * sizeof(pde::Fp8QuantEntry)), srcs[0].options());
+  return {table, std::min<long>(tiles, 256)};
+}
+
+// One tensor without a table: the entry is a kernel argument, so the source may be another tensor every call.
+void fp8_quant_one(const Tensor& src, Tensor& dst, const Tensor& dst_t, Tensor& recs, int64_t rec, int64_t fmt) {
+  TORCH_CHECK(fmt == pde::kE4M3 || fmt == pde::kE5M2, "fp8_quant_one: format is 0 (e4m3) or 1 (e5m2)");
+  const pde::Fp8QuantEntry e = fp8_entry(src, dst, dst_t, rec, recs, "fp8_quant_one");
+  check(pde::fp8_quant_one(static_cast<int>(fmt), e, reinterpret_cast<pde::Fp8Rec*>(recs.data_ptr<float>()),
+                           cur_stream()),
+        "fp8_quant_one");
+}
+
+void fp8_quant(const Tensor& table, int64_t n, int64_t blocks_x, Tensor& recs, int64_t fmt, int64_t table_recs) {
+  CHECK_IN(table);
+  TORCH_CHECK(table_recs == recs.size(0), "fp8_quant: the table was built for ", table_recs, " scale records, recs has ",
+              recs.size(0));
+  TORCH_CHECK(blocks_x > 0 && blocks_x <= 65535, "fp8_quant: blocks_x");
+  TORCH_CHECK(n > 0 && table.numel() == static_cast<long>(n * sizeof(pde::Fp8QuantEntry)), "fp8_quant: table");
+  TORCH_CHECK(fmt == pde::kE4M3 || fmt == pde::kE5M2, "fp8_quant: format is 0 (e4m3) or 1 (e5m2)");
+  check(pde::fp8_quant(static_cast<int>(fmt), reinterpret_cast<const pde::Fp8QuantEntry*>(table.data_ptr()),
+                       static_cast<int>(n), static_cast<int>(blocks_x), fp8_recs(recs, 0, "fp8_quant"), cur_stream()),
+        "fp8_quant");
+}
+
+// role "fwd": a e4m3 [M][Kp] x b e4m3 [N][Kp]; with q / qt / rec_out the quantising epilogue (bias + ReLU -> e4m3 in
+// both layouts), else fp32 `out` (+ bias).  "dgrad": a e5m2; with q / qt / rec_out / mask the masked e5m2 epilogue,
+// else fp32 `out`.  "wgrad": a e5m2; fp32 `out` (+ `gbias`, the row sums of a), stored or added (accumulate).
+void fp8_gemm(const std::string& role, const Tensor& a, const Tensor& b, int64_t M, int64_t N, Tensor& recs,
+              int64_t rec_a, int64_t rec_b, const optional<Tensor>& bias, const optional<Tensor>& out,
+              const optional<Tensor>& q, const optional<Tensor>& qt, int64_t rec_out, const optional<Tensor>& mask,
+              const optional<Tensor>& gbias, bool accumulate) {
+  const bool fwd = role == "fwd", dgrad = role == "dgrad", wgrad = role == "wgrad";
+  TORCH_CHECK(fwd || dgrad || wgrad, "fp8_gemm: role is 'fwd', 'dgrad' or 'wgrad', not '", role, "'");
+  // (the M tiles, of 32 rows at the least, are the grid's y dimension: at most 65535 of them)
+  TORCH_CHECK(M > 0 && N > 0 && M <= (1 << 20) && N < (1 << 24), "fp8_gemm: 1 <= M <= 2^20, 1 <= N < 2^24");
+  pde::Fp8GemmArgs g{};
+  g.A = fp8_mat(a, M, 128, 128, "fp8_gemm: a").data_ptr<uint8_t>();
+  g.B = fp8_mat(b, N, 128, 128, "fp8_gemm: b").data_ptr<uint8_t>();
+  TORCH_CHECK(a.size(1) == b.size(1), "fp8_gemm: a and b must share the padded K pitch");
+  g.M = M; g.N = N; g.Kp = a.size(1);
+  pde::Fp8Rec* r = fp8_recs(recs, std::max({rec_a, rec_b, rec_out}), "fp8_gemm");
+  TORCH_CHECK(rec_a >= 0 && rec_b >= 0, "fp8_gemm: operand scale records");
+  g.recA = r + rec_a; g.recB = r + rec_b;
+  g.accumulate = accumulate;
+  const bool quant = q.has_value() && q->defined();
+  int epi = wgrad ? pde::kFp8Wgrad : !quant ? pde::kFp8F32 : fwd ? pde::kFp8FwdQ : pde::kFp8DgradQ;
+  if (bias.has_value() && bias->defined()) {
+    TORCH_CHECK(fwd, "fp8_gemm: only the forward role takes a bias");
+    CHECK_IN(*bias); CHECK_F32(*bias); TORCH_CHECK(bias->numel() == N, "fp8_gemm: bias size");
+    g.bias = bias->data_ptr<float>();
+  }
+  if (epi == pde::kFp8FwdQ || epi == pde::kFp8DgradQ) {
+    TORCH_CHECK(!wgrad && qt.has_value() && qt->defined() && rec_out >= 0, "fp8_gemm: q needs qt and rec_out");
+    g.q = fp8_mat(*q, M, N, 64, "fp8_gemm: q").data_ptr<uint8_t>(); g.ldq = q->size(1);
+    g.qt = fp8_mat(*qt, N, M, 64, "fp8_gemm: qt").data_ptr<uint8_t>(); g.ldqt = qt->size(1);
+    g.recO = r + rec_out;
+    if (epi == pde::kFp8FwdQ) {
+      TORCH_CHECK(g.bias != nullptr, "fp8_gemm: the quantising forward epilogue needs the bias");
+    } else {
+      TORCH_CHECK(mask.has_value() && mask->defined(), "fp8_gemm: the quantising dgrad epilogue needs the mask");
+      g.mask = fp8_mat(*mask, M, N, 16, "fp8_gemm: mask").data_ptr<uint8_t>(); g.ldmask = mask->size(1);
+    }
+  } else {
+    TORCH_CHECK(out.has_value() && out->defined(), "fp8_gemm: fp32 `out` needed");
+    CHECK_DEV(*out); CHECK_F32(*out);
+    TORCH_CHECK(out->dim() == 2 && out->size(0) == M && out->size(1) == N && out->stride(1) == 1, "fp8_gemm: out is [M][N]");
+    g.out = out->data_ptr<float>(); g.ldo = out->stride(0);
+    if (gbias.has_value() && gbias->defined()) {
+      TORCH_CHECK(wgrad, "fp8_gemm: only the weight-gradient role writes a bias gradient");
+      CHECK_IN(*gbias); CHECK_F32(*gbias); TORCH_CHECK(gbias->numel() == M, "fp8_gemm: gbias size");
+      g.gbias = gbias->data_ptr<float>();
+    }
+  }
+  check(pde::fp8_gemm(fwd ? pde::kE4M3 : pde::kE5M2, pde::kE4M3, epi, g, cur_stream()), "fp8_gemm");
+}
+
+void fp8_scales(Tensor& recs) {
+  pde::Fp8Rec* r = fp8_recs(recs, 0, "fp8_scales");
+  check(pde::fp8_scales(r, static_cast<int>(recs.size(0)), cur_stream()), "fp8_scales");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1779,6 +1920,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("log_softmax_bwd", &log_softmax_bwd);
   m.def("mse_fwd", &mse_fwd);
   m.def("mse_bwd", &mse_bwd);
+  m.def("fp8_quant_table", &fp8_quant_table, py::arg("srcs"), py::arg("dsts"), py::arg("dsts_t"), py::arg("rec"),
+        py::arg("recs"));
+  m.def("fp8_quant", &fp8_quant, py::arg("table"), py::arg("n"), py::arg("blocks_x"), py::arg("recs"), py::arg("fmt"),
+        py::arg("table_recs"));
+  m.def("fp8_quant_one", &fp8_quant_one, py::arg("src"), py::arg("dst"), py::arg("dst_t"), py::arg("recs"),
+        py::arg("rec"), py::arg("fmt"));
+  m.def("fp8_gemm", &fp8_gemm, py::arg("role"), py::arg("a"), py::arg("b"), py::arg("M"), py::arg("N"), py::arg("recs"),
+        py::arg("rec_a"), py::arg("rec_b"), py::kw_only(), py::arg("bias") = py::none(), py::arg("out") = py::none(),
+        py::arg("q") = py::none(), py::arg("qt") = py::none(), py::arg("rec_out") = -1, py::arg("mask") = py::none(),
+        py::arg("gbias") = py::none(), py::arg("accumulate") = false);
+  m.def("fp8_scales", &fp8_scales);
   m.def("optim_table", &optim_table);
   m.def("optim_step", &optim_step);
   m.def("optim_trust_table", &optim_trust_table);

@@ -92,7 +92,8 @@ def _native_grid() -> int:
 
 class Trainer:
     def __init__(self, ctx, model, train_data, test_data, make_opt, criterion, save_every, snapshot_path,
-                 log, metrics=None, save_optimizer=True, fused=False, ddp_kwargs=None, fast=None, graph_chunk=50):
+                 log, metrics=None, save_optimizer=True, fused=False, ddp_kwargs=None, fast=None, graph_chunk=50,
+                 precision="bf16"):
         self.ctx = ctx
         self.global_rank = int(os.environ.get("RANK", ctx.rank))
         self.local_rank = int(os.environ.get("LOCAL_RANK", ctx.local_rank))
@@ -116,6 +117,10 @@ class Trainer:
         on_gpu = ctx.device.type == "cuda"
         is_cnn = type(self.model).__name__ == "Net"
         fast = on_gpu if fast is None else fast
+        self.fp8 = precision == "fp8"
+        if self.fp8 and (is_cnn or not (on_gpu and fast)):
+            raise SystemExit("--precision fp8 is the fused MLP step on the GPU: not --model cnn, --layers or the CPU")
+        self._fp8_calibrated = False
         if fused and not on_gpu:
             raise SystemExit("--fused runs the gfx950 training kernel: it needs a GPU")
         if fast and not on_gpu:
@@ -132,7 +137,7 @@ class Trainer:
             from ..models.mlp_fused import FusedMLP
             from ..parallel.comm import data_plane
 
-            self.fmlp = FusedMLP(self.model)
+            self.fmlp = FusedMLP(self.model, precision=precision)
             self.ddp = DistributedDataParallel(self.model, overlap=False, comm=data_plane(ctx), **(ddp_kwargs or {}))
             # one launch per step at any world size on one node: at world > 1 the gradient average runs inside the
             # launch over xGMI (MegaMLP.exchange) -- every rank must own its GPU (the persistent grid fills it)
@@ -141,7 +146,8 @@ class Trainer:
             single_node = int(os.environ.get("LOCAL_WORLD_SIZE", str(world))) == world
             # (the one-launch step applies the update itself: only the kinds it knows, _MODES, and no global-norm
             # clipping -- --clip_grad_norm takes the route --optimizer lamb takes: FusedMLP + optimizer.step())
-            if (train_data.batch_size % 32 == 0 and os.environ.get("PDE_MLP_MEGA", "1") != "0" and
+            # (--precision fp8: the FP8 GEMMs live in FusedMLP, so that route + optimizer.step())
+            if (not self.fp8 and train_data.batch_size % 32 == 0 and os.environ.get("PDE_MLP_MEGA", "1") != "0" and
                     getattr(self.optimizer, "KIND", "") in _MODES and self.optimizer.clip_max_norm() is None and
                     (world == 1 or (own_gpu and single_node and getattr(self.optimizer, "KIND", "") != "sgd"))):
                 from ..models.mlp_mega import MegaMLP
@@ -245,11 +251,18 @@ class Trainer:
         loss = None
         if self.runner is not None:  # hipGraph chunks over the epoch's gathered shard (utils/epoch_graph.py)
             self.epoch_batches.fill(epoch)
+            if self.fp8 and not self._fp8_calibrated:
+                # scales from the first batch, before anything is captured
+                self.fmlp.calibrate(*self.epoch_batches.batch(0))
+                self._fp8_calibrated = True
             n, loss = self.runner.run(on_steps=self._after_steps)
             self.epoch_batches.prepare(epoch + 1)  # host work while the GPU drains this epoch's replays
         else:
             self.train_data.set_epoch(epoch)
             for source, targets in self.train_data:
+                if self.fp8 and not self._fp8_calibrated:
+                    self.fmlp.calibrate(source, targets)
+                    self._fp8_calibrated = True
                 loss = self._run_batch(source, targets)
                 n += source.shape[0]
         if self.ctx.device.type == "cuda":
@@ -338,6 +351,9 @@ def build_parser():
                         help="cnn: whole-network fused training kernel (GPU; the default GPU path, kept for scripts)")
     parser.add_argument("--layers", action="store_true",
                         help="GPU: layer-by-layer autograd + DDP hooks instead of the fused / one-launch step")
+    parser.add_argument("--precision", default="bf16", choices=["bf16", "fp8"],
+                        help="--model mlp on the GPU: fp8 = e4m3 / e5m2 GEMMs with per-tensor delayed scaling, "
+                             "fp32 master weights (default: bf16)")
     parser.add_argument("--graph_chunk", type=int, default=50, help="GPU: training steps per hipGraph replay")
     parser.add_argument("--device", default="auto", choices=["auto", "cpu", "gpu"])
     parser.add_argument("--snapshot_path", default="snapshot.pt")
@@ -356,9 +372,12 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
     cfg = rtconfig.apply(rtconfig.from_args(args))
     args.device = rtconfig.device_for(cfg, args.device)
+    if args.precision == "fp8" and (args.model == "cnn" or args.rewire or args.device == "cpu"):
+        parser.error("--precision fp8 needs --model mlp on the GPU, without --rewire")
 
     start = time.time()
     if args.rewire and args.optimizer in ("lamb", "lars"):
@@ -386,7 +405,7 @@ def main(argv=None):
         trainer = Trainer(ctx, model, train_data, test_data, make_opt, criterion, args.save_every,
                           args.snapshot_path, log, metrics, fused=args.fused and args.model == "cnn",
                           ddp_kwargs=cfg.ddp_kwargs(), fast=False if args.layers else None,
-                          graph_chunk=args.graph_chunk)
+                          graph_chunk=args.graph_chunk, precision=args.precision)
         trainer.train(args.total_epochs)
         pdist.shutdown()
     end = time.time()

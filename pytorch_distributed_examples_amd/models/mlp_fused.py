@@ -37,13 +37,104 @@ def _pad8(n: int) -> int:
 
 
 class FusedMLP:
-    def __init__(self, net):
+    """``precision="fp8"`` (opt-in, GPU only): the same step on the FP8 GEMM of ``csrc/kernels/gemm_fp8.hip`` --
+    e4m3 weights and activations, e5m2 gradients, per-tensor power-of-two scales from the previous step's maxima
+    (:mod:`..ops.fp8`), fp32 accumulation, fp32 master weights and fp32 gradients in ``p.grad``.  Per step: one
+    weight-quantise launch, one input-quantise launch, L forward GEMMs (bias + ReLU + quantise + transpose in the
+    epilogue), ``ce_fused``, one d-logits quantise launch, L weight-gradient GEMMs (bias gradient inside) and L-1
+    data-gradient GEMMs (ReLU mask + quantise + transpose in the epilogue), one scale-update launch."""
+
+    def __init__(self, net, precision: str = "bf16"):
+        if precision not in ("bf16", "fp8"):
+            raise ValueError(f"precision must be 'bf16' or 'fp8', not {precision!r}")
         self.net = net
+        self.precision = precision
         self.layers = [net.input_layer, *net.hidden_layers, net.final_layer]
         for i, L in enumerate(self.layers):
             assert L.bias is not None, "the fused step routes every bias gradient through the ones column"
             assert L.relu == (i < len(self.layers) - 1), "ReLU after every layer but the last"
         self._bufs: dict = {}
+        self._fp8: dict = {}
+
+    # ---- FP8 path ------------------------------------------------------------------------------------------
+    def _fp8_state(self, B: int, dev: torch.device):
+        """Records (shared by every batch size), weight buffers and table, and the per-batch-size buffers.  Nothing
+        here depends on the input tensor: the input and d logits are quantised by table-free launches."""
+        from ..ops import fp8
+
+        n = len(self.layers)
+        st = self._fp8
+        if "rec" not in st:
+            # record i: input of layer i; n + i: weight i; 2n + i: gradient of layer i's output
+            st["rec"] = fp8.ScaleRecords([fp8.E4M3] * (2 * n) + [fp8.E5M2] * n, dev)
+            st["wq"] = [fp8.buffer(L.out_features, L.in_features, dev) for L in self.layers]
+            st["wqt"] = [fp8.buffer(L.in_features, L.out_features, dev) for L in self.layers]
+        wkey = tuple(L.weight.data_ptr() for L in self.layers)
+        if st.get("wkey") != wkey:  # first use, or the parameters moved: the weight quantiser's table is rebuilt
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FusedMLP(precision='fp8'): the weights moved since the last eager step; run one "
+                                   "step (or calibrate) before graph capture")
+            st["wkey"] = wkey
+            st["wplan"] = fp8.QuantPlan(st["rec"], fp8.E4M3, [L.weight.detach() for L in self.layers], st["wq"],
+                                        st["wqt"], [n + i for i in range(n)])
+        if B not in st:
+            feats = [self.layers[0].in_features] + [L.out_features for L in self.layers]
+            st[B] = dict(
+                aq=[fp8.buffer(B, f, dev) for f in feats[:-1]], aqt=[fp8.buffer(f, B, dev) for f in feats[:-1]],
+                dq=[fp8.buffer(B, f, dev) for f in feats[1:]], dqt=[fp8.buffer(f, B, dev) for f in feats[1:]],
+                logits=torch.empty(B, feats[-1], dtype=torch.float32, device=dev),
+                dlog=torch.zeros(B, _pad8(feats[-1]), dtype=torch.bfloat16, device=dev))
+        return st, st[B]
+
+    def _forward_backward_fp8(self, x, y, accumulate):
+        from ..ops import fp8
+
+        if not x.is_cuda:
+            raise ValueError("precision='fp8' runs on the GPU only (the FP8 GEMM is a gfx950 kernel)")
+        C = _native.C()
+        B, n = x.shape[0], len(self.layers)
+        xs = x.reshape(B, -1)  # the quantiser reads fp32 or bf16 rows of any pitch, wherever they are
+        if xs.dtype not in (torch.float32, torch.bfloat16):
+            xs = xs.float()
+        if xs.stride(1) != 1:
+            xs = xs.contiguous()
+        st, b = self._fp8_state(B, x.device)
+        rec, last = st["rec"].t, n - 1
+        st["wplan"].run()
+        fp8.quantise(st["rec"], fp8.E4M3, xs, b["aq"][0], b["aqt"][0], 0)
+        for i, L in enumerate(self.layers):
+            if i < last:
+                C.fp8_gemm("fwd", b["aq"][i], st["wq"][i], B, L.out_features, rec, i, n + i, bias=L.bias.detach(),
+                           q=b["aq"][i + 1], qt=b["aqt"][i + 1], rec_out=i + 1)
+            else:
+                C.fp8_gemm("fwd", b["aq"][i], st["wq"][i], B, L.out_features, rec, i, n + i, bias=L.bias.detach(),
+                           out=b["logits"])
+        loss, _ = C.ce_fused(b["logits"], y.long().contiguous(), b["dlog"])
+        fp8.quantise(st["rec"], fp8.E5M2, b["dlog"][:, :self.layers[-1].out_features], b["dq"][-1], b["dqt"][-1],
+                     3 * n - 1)
+        for i in range(last, -1, -1):
+            L = self.layers[i]
+            gw, gb = self._grads(L)
+            C.fp8_gemm("wgrad", b["dqt"][i], b["aqt"][i], L.out_features, L.in_features, rec, 2 * n + i, i,
+                       out=gw, gbias=gb, accumulate=accumulate)
+            if i > 0:
+                C.fp8_gemm("dgrad", b["dq"][i], st["wqt"][i], B, L.in_features, rec, 2 * n + i, n + i,
+                           q=b["dq"][i - 1], qt=b["dqt"][i - 1], rec_out=2 * n + i - 1, mask=b["aq"][i])
+        st["rec"].update()
+        return loss
+
+    @torch.no_grad()
+    def calibrate(self, x: torch.Tensor, y: torch.Tensor) -> None:
+        """One FP8 pass that only sets the scales (the first real step then does not run on the initial scales
+        of 1); the gradients it leaves are overwritten by the next step."""
+        if self.precision != "fp8":
+            raise ValueError("calibrate() belongs to precision='fp8'")
+        self._forward_backward_fp8(x, y, False)
+
+    def fp8_scales(self) -> dict:
+        """The current scales: {'act': [...], 'weight': [...], 'grad': [...]}, one per layer (after a step)."""
+        s, n = self._fp8["rec"].scales(), len(self.layers)
+        return {"act": s[:n], "weight": s[n:2 * n], "grad": s[2 * n:]}
 
     def _buffers(self, B: int, dev: torch.device):
         key = (B, str(dev))
@@ -77,7 +168,11 @@ class FusedMLP:
         the optimiser step is folded into the backward: layer i+1's update runs as extra blocks of layer i's
         paired dgrad + wgrad launch (its gradients are final by then, and no GEMM of that launch touches its
         weights), layers 1 and 0 in one closing launch.  Replaces ``opt.step()``; same update math, same
-        kernels' device code."""
+        kernels' device code.  Not available with ``precision="fp8"`` (ValueError)."""
+        if self.precision == "fp8":
+            if opt is not None:
+                raise ValueError("precision='fp8' does not fold the optimiser into the backward: call opt.step()")
+            return self._forward_backward_fp8(x, y, accumulate)
         C = _native.C()
         params_of = [[L.weight, L.bias] for L in self.layers]
         fuse_opt = (opt is not None and not streams.active_for(x) and
@@ -133,4 +228,6 @@ class FusedMLP:
     def launches_per_step(self) -> int:
         """Kernel launches of one forward_backward (split-K GEMMs add their reduce launch on top)."""
         n = len(self.layers)
+        if self.precision == "fp8":  # + weight quantise, d-logits quantise and the scale update
+            return 2 + n + 2 + n + (n - 1) + 1
         return 1 + n + 1 + n + (n - 1)
