@@ -1,5 +1,6 @@
 """The one-launch MLP training step (csrc/kernels/mlp_fused.hip, models/mlp_mega.py) against the layer-by-layer
-fused path (FusedMLP + the optimiser's own launch) and a plain fp32 PyTorch reference of the same step."""
+fused path (FusedMLP + the optimiser's own launch) and a plain fp32 PyTorch reference of the same step.
+Element-level checks of every phase against float64: test_mlp_mega_exact_gpu.py (mlp_mega_exact.py)."""
 import pytest
 import torch
 
